@@ -6,15 +6,31 @@ One bench "step" = one COMPLETE solve exactly as the reference times it: field i
 error check vs the analytic solution every 2nd step → global error log on the host. Nothing is cached between solves:
 every solve re-initialises the fields and recomputes all K steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set up, W untimed solves, the K timed solves, the JSON line (the
+timed solves' own error log is checked against the closed-form oracle in every run: a formula over its ~10 rows, no
+solve). ``--full`` adds what takes a run of its own: the traced per-phase breakdown solve (``phases_ms``, null in a
+plain run; ``--no-phases`` skips it).
+
+``--dump-outputs DIR`` writes what the last timed solve computed, after the timed block, as float64 ``.npy`` files:
+``error_log.npy`` (one row ``[step, L-inf, RMS]`` per checked step: what the solve returns) and ``u_final.npy``, the
+field u^K on the (N+1)³ nodes. A field above 48 MB (the headline 513³ is 1.08 GB) is written as a fixed sample: the
+values at the sorted unique flat C-order indices of ``numpy.random.default_rng(DUMP_SEED).integers(0, (N+1)**3,
+DUMP_SAMPLE)``, so two builds run with the same arguments write arrays that compare element for element (the inputs
+are the analytic initial condition: identical from run to run). ``--python`` on several ranks writes each rank's own
+part as ``u_final.rank<r>.npy`` (the ranks share the size limits); the line's ``dump_outputs`` says what was written.
+While the run lasts, DIR also holds the native ranks' raw dump of the whole field (``u_final.raw*``: 8·(N+1)³ bytes,
+1.08 GB at 513³, 69 GB at N = 2048), which rank 0 samples and removes, also when the run fails.
 
 What runs: every rank starts the native runtime (``bin/wave3d``, C++ + HIP kernels + RCCL, built in-tree) as a child
 process on its GPU and hands it the launch (RANK / LOCAL_RANK / WORLD_SIZE from torchrun, a per-launch rendezvous
 nonce for the RCCL unique id). The child runs W untimed solves (plus, on several ranks, the schedule autotune, whose
 candidate solves are untimed too), then EXACTLY K solves between a device sync + RCCL barrier on both sides, and reports
 the interval as the max over ranks. This process only orchestrates (torch.distributed over gloo: nonce broadcast and
-the agreement on success); it never touches the GPU. The child runs on the system ROCm (HIP 7.2 + RCCL 2.27), whose
+the agreement on success) and loads the in-tree extension ``mpi_cuda_amd._C`` of the same build (``_extension``; no HIP
+call); it never touches the GPU. The child runs on the system ROCm (HIP 7.2 + RCCL 2.27), whose
 stream capture of the multi-rank schedules is verified; the HIP 7.0 runtime bundled with PyTorch crashes in
 hipStreamEndCapture on those graphs (tools/probes/capture_probe*.hip, csrc/src/solver_gpu.cpp multistream_capture_safe).
 
@@ -50,6 +66,10 @@ sys.path.insert(0, ROOT)
 REF_GCELL = {1: 512**3 * 20 / 0.752 / 1e9, 2: 512**3 * 20 / 0.505 / 1e9}
 REF_FINAL_LINF = 3.960129e-09  # report.pdf p.16 §4.3.1, step 20
 CLI = os.path.join(ROOT, "bin", "wave3d")
+DUMP_WHOLE_BYTES = 48 << 20  # --dump-outputs: a field up to this size is written whole, a larger one as a sample
+DUMP_SAMPLE = 4 << 20        # ... of this many draws (32 MB of float64 values before duplicates are dropped)
+DUMP_SEED = 20240519
+DUMP_RAW = "u_final.raw"        # ... and the name of the ranks' transient raw dumps in DIR
 
 
 def _args(argv=None):
@@ -70,7 +90,11 @@ def _args(argv=None):
     ap.add_argument("--no-autotune", action="store_true",
                     help="several ranks: use --decomp/--temporal as given instead of timing the candidate schedules")
     ap.add_argument("--autotune", action="store_true", help="time the candidate schedules even on one rank")
-    ap.add_argument("--no-phases", action="store_true", help="skip the traced per-phase breakdown solve")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the traced per-phase breakdown solve (phases_ms)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed solve's error log and field u^K (sampled when large) as DIR/<name>.npy")
+    ap.add_argument("--no-phases", action="store_true", help="--full: skip the traced per-phase breakdown solve")
     ap.add_argument("--cpu", action="store_true", help="native CPU ranks (contract test without a GPU)")
     ap.add_argument("--python", action="store_true", help="in-process Python Solver instead of the native runtime")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "torch"], help="--python: halo transport")
@@ -152,8 +176,74 @@ def _correct(a, finite, steps) -> tuple[bool, str]:
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------------------------
+def _dump_index(n: int, files: int = 1):
+    """Flat C-order indices of the n-node field that --dump-outputs writes: all of them, or the fixed sample (``files``:
+    how many such files share the size limits)."""
+    import numpy as np
+
+    if n * 8 * files <= DUMP_WHOLE_BYTES:
+        return np.arange(n, dtype=np.int64), "whole field"
+    draws = DUMP_SAMPLE // files
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, draws, dtype=np.int64))
+    return idx, f"{idx.size} of {n} nodes: sorted unique default_rng({DUMP_SEED}).integers(0, {n}, {draws})"
+
+
+def _dump_log(dirname: str, steps) -> None:
+    import numpy as np
+
+    np.save(os.path.join(dirname, "error_log.npy"), np.asarray(steps, dtype=np.float64).reshape(-1, 3))
+
+
+def _dump_native_field(dirname: str, prefix: str) -> str:
+    """u_final.npy from the wave3d-dump-v1 files the native ranks wrote at ``prefix`` (run_native removes them)."""
+    import numpy as np
+
+    from mpi_cuda_amd.utils.dump import read_meta
+
+    metas = read_meta(prefix)
+    shape = tuple(metas[0]["global_shape"])
+    idx, what = _dump_index(int(np.prod(shape)))
+    x, y, z = np.unravel_index(idx, shape)
+    out = np.full(idx.size, np.nan)
+    for m in metas:
+        box = np.memmap(m["_bin"], dtype="<f8", mode="r", shape=tuple(m["shape"]))
+        (ox, oy, oz), (sx, sy, sz) = m["offset"], m["shape"]
+        own = (x >= ox) & (x < ox + sx) & (y >= oy) & (y < oy + sy) & (z >= oz) & (z < oz + sz)
+        out[own] = box[x[own] - ox, y[own] - oy, z[own] - oz]
+        del box
+    np.save(os.path.join(dirname, "u_final.npy"), out.reshape(shape) if idx.size == np.prod(shape) else out)
+    return what
+
+
+def _dump_python_field(dirname: str, solver, rank: int, world: int) -> str:
+    import numpy as np
+
+    u = solver.owned_field(0).numpy()
+    idx, what = _dump_index(u.size, world)
+    name = "u_final.npy" if world == 1 else f"u_final.rank{rank}.npy"
+    np.save(os.path.join(dirname, name), u if idx.size == u.size else u.reshape(-1)[idx])
+    return what
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # native runtime (default)
 # ------------------------------------------------------------------------------------------------------------------
+def _extension():
+    """The in-tree extension ``mpi_cuda_amd._C``: tools/build.py links it and ``bin/wave3d`` from the same objects, so
+    the benchmark process holds the build it reports on. Like a missing CLI, a missing extension is an error (it is
+    not built from here: a benchmark run does not compile)."""
+    import importlib
+
+    import torch  # noqa: F401  (torch's HIP runtime first, as mpi_cuda_amd._native does; no HIP call is made)
+
+    try:
+        return importlib.import_module("mpi_cuda_amd._C")
+    except ImportError as e:
+        raise SystemExit(f"bench: native extension mpi_cuda_amd._C does not load ({e}) (python tools/build.py)")
+
+
 def _agree(ok: int, world: int) -> int:
     if world == 1:
         return ok
@@ -262,8 +352,20 @@ def _qualify_sdma(a, rank: int, world: int, local: int) -> tuple[bool, str]:
 
 
 def run_native(a, rank: int, world: int, local: int) -> int:
+    try:
+        return _run_native(a, rank, world, local)
+    finally:  # the ranks' raw --dump files never outlive the run, whichever way it ends
+        if a.dump_outputs and rank == 0:
+            import glob
+
+            for path in glob.glob(os.path.join(glob.escape(os.path.abspath(a.dump_outputs)), DUMP_RAW + "*")):
+                os.remove(path)
+
+
+def _run_native(a, rank: int, world: int, local: int) -> int:
     if not os.path.exists(CLI):
         raise SystemExit(f"bench: native runtime {CLI} is missing (python tools/build.py)")
+    C = _extension()
     multi = world > 1
     warm = max(a.warmup, 2 if multi else 1)
     temporal = 1 if a.no_temporal else a.temporal
@@ -278,6 +380,11 @@ def run_native(a, rank: int, world: int, local: int) -> int:
         warm = max(warm, 8)
     base = [str(a.N), repr(a.tau), str(a.K), repr(a.L), "--quiet", "--warmup", str(warm - 1), "--repeat", "1",
             "--bench-steps", str(a.steps)]
+    dump_prefix = ""
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        dump_prefix = os.path.join(os.path.abspath(a.dump_outputs), DUMP_RAW)
+        base += ["--dump", dump_prefix]  # (written right after the timed block: u^K of the last timed solve)
     cmd = base + ["--decomp", a.decomp, "--temporal", str(temporal)]
     if a.cpu:
         cmd.append("--cpu")
@@ -290,7 +397,7 @@ def run_native(a, rank: int, world: int, local: int) -> int:
             cmd.append("--autotune")
             if autotune_sdma:
                 cmd.append("--autotune-sdma")
-        if not a.no_phases:
+        if a.full and not a.no_phases:
             cmd.append("--phases")
         if a.no_overlap:
             cmd.append("--no-overlap")
@@ -323,7 +430,7 @@ def run_native(a, rank: int, world: int, local: int) -> int:
             if a.no_rccl:  # (no RCCL at all: the transport the run asked for, host collectives through files)
                 safe += ["--no-rccl", "--transport", a.native_transport]
                 via = a.native_transport
-            if not a.no_phases:
+            if a.full and not a.no_phases:
                 safe.append("--phases")
         run = _child(a, rank, world, local, safe, "fallback")
         fallback = {"schedule": "slab-S4-seq, no autotune" + ("" if a.cpu else ", " + via), "first_failure": first}
@@ -340,11 +447,16 @@ def run_native(a, rank: int, world: int, local: int) -> int:
     if rank == 0:
         bench_s = float(res["bench_s"])
         ms = bench_s / a.steps * 1e3
-        value = (a.N ** 3 * a.K) / (ms / 1e3) / 1e9
+        value = C.Problem(a.N, a.tau, a.K, a.L).cell_updates / (ms / 1e3) / 1e9  # N³·K as the ranks count it
         steps = res.get("steps") or []
         final_linf = steps[-1][1] if steps else float("nan")
         final_rms = steps[-1][2] if steps else None
         correct, why_correct = _correct(a, res.get("finite", False), steps)
+        dumped = None
+        if a.dump_outputs:
+            _dump_log(a.dump_outputs, steps)
+            dumped = {"error_log": "[step, L-inf, RMS] per checked step",
+                      "u_final": _dump_native_field(a.dump_outputs, dump_prefix)}
         dims = res.get("dims", [1, 1, 1])
         sched = res.get("schedule", "")
         par = (f"{sched.split('-')[0]}{world}" if multi else "single") if not a.cpu else f"cpu-ranks{world}"
@@ -385,6 +497,8 @@ def run_native(a, rank: int, world: int, local: int) -> int:
             "phases_ms": res.get("phases_ms"),
             "distinct_gpus": None if a.cpu else _distinct_gpus(world),
         }
+        if dumped:
+            extra["dump_outputs"] = dumped
         if fallback is not None:
             extra["fallback_schedule"] = fallback["schedule"]
             extra["first_failure"] = fallback["first_failure"]
@@ -480,7 +594,15 @@ def run_python(a, rank: int, world: int, local: int, degraded: str = "") -> int:
     ms = float(t[0]) / a.steps * 1e3
     value = spec.cell_updates / (ms / 1e3) / 1e9
     final_linf = r.max_err[-1] if r.max_err else float("nan")
-    correct, why_correct = _correct(a, r.finite, [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)])
+    log = [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]
+    correct, why_correct = _correct(a, r.finite, log)
+    dumped = None
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        dumped = {"u_final": _dump_python_field(a.dump_outputs, solver, rank, world)}
+        if rank == 0:
+            _dump_log(a.dump_outputs, log)
+            dumped["error_log"] = "[step, L-inf, RMS] per checked step"
     if rank == 0:
         py_loop = transport == "torch"
         dims = "x".join(str(d) for d in solver.dims)
@@ -496,10 +618,12 @@ def run_python(a, rank: int, world: int, local: int, degraded: str = "") -> int:
                  "correct": correct, "correct_check": why_correct, "degraded": bool(degraded)}
         if degraded:
             extra["degraded_reason"] = degraded
+        if dumped:
+            extra["dump_outputs"] = dumped
         _emit(a, _line(a, world, value, ms, cfg, extra))
     if world > 1:
         dist.barrier()
-    return (0 if correct else 1) if not degraded else (0 if correct else 1)
+    return 0 if correct else 1
 
 
 def main(argv=None) -> int:

@@ -336,6 +336,8 @@ int run_gpu(const Args& a) {
              " produced a different error log than the warmup solve");
     r = rs.back();
   }
+  // --dump: u^K of the last solve above (before the traced solve below overwrites the fields with its own)
+  if (!a.dump.empty()) write_dump(a.dump, a.prob, s->layout(), s->download(0), rank, world, s->dims());
   // per-phase breakdown of the schedule that was timed: one more solve with the same kernels, traced with events
   PhaseTimes ph;
   if (a.phases && !a.timers) {
@@ -442,7 +444,6 @@ int run_gpu(const Args& a) {
         << ", \"schedule\": \"" << s->mode() << "\", \"shell_ms\": " << u.shell_ms << ", \"comm_ms\": " << u.comm_ms
         << ", \"compute_ms\": " << u.compute_ms << ", \"check_ms\": " << u.check_ms << "}\n";
   }
-  if (!a.dump.empty()) write_dump(a.dump, a.prob, s->layout(), s->download(0), rank, world, d);
   if (!a.checkpoint.empty())
     write_checkpoint(a.checkpoint, a.prob, s->layout(), s->download(0), s->download(1), rank, world, d);
   if ((s->push() || s->sdma()) && !comm && !fake)

@@ -8,10 +8,10 @@ OUT=${1:-scaling.jsonl}; GPUS=${GPUS:-"1 2 4 8"}
 : > "$OUT"
 for n in $GPUS; do
   if [ "$n" = 1 ]; then
-    timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 3 --out "$OUT" || exit $?
+    timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 3 --full --out "$OUT" || exit $?
   else
     timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 \
-      --master-port $((29500 + n)) bench.py --gpus "$n" --steps 20 --warmup 3 --out "$OUT" || exit $?
+      --master-port $((29500 + n)) bench.py --gpus "$n" --steps 20 --warmup 3 --full --out "$OUT" || exit $?
   fi
 done
 python tools/scaling_report.py "$OUT"
@@ -22,6 +22,6 @@ python tools/scaling_report.py "$OUT"
 # and keeps the fastest whose log and fields match.
 if echo " $GPUS " | grep -q " 8 "; then
   timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-    --master-port 29599 bench.py --gpus 8 --N 2048 --tau 2.5e-4 --autotune-sdma --steps 3 --warmup 2 \
+    --master-port 29599 bench.py --gpus 8 --N 2048 --tau 2.5e-4 --autotune-sdma --steps 3 --warmup 2 --full \
     --out "${OUT%.jsonl}_2048.jsonl" || exit $?
 fi

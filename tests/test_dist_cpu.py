@@ -86,12 +86,22 @@ def test_bench_python_path_cpu_labels_step_loop(tmp_path):
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29430 + os.getpid() % 50), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu",
-           "--python", "--N", "24", "--steps", "2", "--warmup", "1"]
+           "--python", "--N", "24", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")]
     out = subprocess.run(cmd, check=True, timeout=300, capture_output=True, text=True).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
     assert d["config"]["schedule"] == "python-step-loop-S1" and d["config"]["transport"] == "torch"
     assert not d["config"]["graph"] and not d["config"]["overlap"] and not d["config"]["temporal_blocking"]
     assert d["correct"] and d["degraded"] is False
+    # --dump-outputs of the in-process path: each rank's own slab of u^K, together the reference field
+    import numpy as np
+
+    from mpi_cuda_amd import ProblemSpec
+    from mpi_cuda_amd.models.wave3d import torch_reference_solve
+
+    _, uk, _ = torch_reference_solve(ProblemSpec(N=24, tau=1e-3, K=20), return_fields=True)
+    parts = [np.load(tmp_path / "dump" / f"u_final.rank{r}.npy") for r in range(2)]
+    assert np.array_equal(np.concatenate(parts, axis=0), uk.numpy())
+    assert np.load(tmp_path / "dump" / "error_log.npy")[-1, 1] == d["final_max_err"]
 
 
 def test_bench_failure_retries_once_with_the_conservative_schedule(tmp_path):
@@ -161,3 +171,73 @@ def test_bench_correct_gate_uses_the_oracle_for_every_config():
     a = _bench_args(N=2048, tau=2.5e-4)
     logged = [[2, 1.553202e-13, 5.485516e-14], [10, 3.875233e-12, 1.370967e-12], [20, 1.549894e-11, 5.483359e-12]]
     assert bench._correct(a, True, logged)[0]
+
+
+def test_bench_plain_run_dumps_the_last_timed_solve(tmp_path):
+    """A plain run does not trace the phases (phases_ms is null: --full does) and --dump-outputs writes what the last
+    timed solve computed: the error log and u^K, here whole and bit-equal to the PyTorch reference; the ranks' raw
+    dump is gone."""
+    import json
+
+    import numpy as np
+
+    from mpi_cuda_amd import ProblemSpec
+    from mpi_cuda_amd.models.wave3d import torch_reference_solve
+
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cpu", "--N", "24", "--K", "6", "--steps",
+           "2", "--warmup", "1", "--dump-outputs", str(d)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = subprocess.run(cmd, check=True, timeout=120, capture_output=True, text=True, env=env).stdout
+    line = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["correct"] is True and line["phases_ms"] is None
+    assert sorted(p.name for p in d.iterdir()) == ["error_log.npy", "u_final.npy"]
+    errs, uk, _ = torch_reference_solve(ProblemSpec(N=24, tau=1e-3, K=6, check_every=2), return_fields=True)
+    u = np.load(d / "u_final.npy")
+    assert u.dtype == np.float64 and u.shape == (25, 25, 25) and np.array_equal(u, uk.numpy())
+    log = np.load(d / "error_log.npy")
+    assert log.dtype == np.float64 and log.shape == (3, 3) and list(log[:, 0]) == [2, 4, 6]
+    assert line["final_max_err"] == log[-1, 1]
+
+
+def test_bench_dump_gathers_the_sample_from_the_rank_files(tmp_path, monkeypatch):
+    """The sampled path of --dump-outputs on a decomposed run: two native CPU ranks dump their boxes, bench.py gathers
+    the fixed sample from the rank files; every value is the PyTorch reference's at that node."""
+    import numpy as np
+
+    from mpi_cuda_amd import ProblemSpec
+    from mpi_cuda_amd.models.wave3d import torch_reference_solve
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    prefix = str(tmp_path / bench.DUMP_RAW)
+    subprocess.run([os.path.join(ROOT, "bin", "wave3d"), "24", "0.001", "6", "--cpu", "--np", "2", "--dump", prefix,
+                    "--quiet"], check=True, timeout=120, capture_output=True)
+    assert os.path.exists(prefix + ".rank1.bin")
+    monkeypatch.setattr(bench, "DUMP_WHOLE_BYTES", 4096)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 3000)
+    what = bench._dump_native_field(str(tmp_path), prefix)
+    idx, _ = bench._dump_index(25 ** 3)
+    assert 2000 < idx.size <= 3000 and what.startswith(f"{idx.size} of {25 ** 3} nodes")
+    _, uk, _ = torch_reference_solve(ProblemSpec(N=24, tau=1e-3, K=6), return_fields=True)
+    u = np.load(tmp_path / "u_final.npy")
+    assert u.dtype == np.float64 and u.shape == idx.shape and np.array_equal(u, uk.numpy().reshape(-1)[idx])
+    assert (idx // 625).min() < 12 and (idx // 625).max() > 12  # (nodes of both ranks' slabs)
+
+
+def test_bench_dump_sample_is_fixed_and_bounded():
+    """A field above the size limit is written at a fixed sample of its nodes: the same sorted indices in every run."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n = 513 ** 3
+    idx, what = bench._dump_index(n)
+    again, _ = bench._dump_index(n)
+    assert np.array_equal(idx, again) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    assert 3 << 20 < idx.size <= bench.DUMP_SAMPLE and idx.size * 8 <= 32 << 20 and str(idx.size) in what
+    whole, _ = bench._dump_index(65 ** 3)
+    assert np.array_equal(whole, np.arange(65 ** 3))

@@ -17,21 +17,12 @@
 #include "wave3d/decomp.hpp"
 #include "wave3d/deep_plan.hpp"
 #include "wave3d/problem.hpp"
+#include "wave3d/tiling.hpp"
 
 namespace wave3d {
 
 // Error partial: x = L∞ candidate, y = Σe².
 using Partial = double2;
-
-// Tiling knobs of the leapfrog kernel (runtime-selectable so the tuner/bench can sweep them).
-struct LeapfrogTiling {
-  int variant = 1;        // 0 = LDS-staged workgroup tile (k_leapfrog_lds), 1 = register-queue waves (k_leapfrog_rq)
-  int rows = 2;           // variant 1: rows (y) per wave held in registers (1, 2, 4 or 8)
-  int ty = 8;             // variant 0: tile rows (y) per workgroup; block = 64 × ty threads
-  int target_blocks = 0;  // x-chunking aims for at least this many work items (v0: workgroups, v1: waves; 0 = auto)
-  bool xcd_remap = true;  // give each XCD a contiguous range of tiles (L2 reuse of tile halos)
-  bool nt_store = true;   // non-temporal stores of u^{n+1} (measured faster on MI355X, profiles/)
-};
 
 // Number of error partials (v0: workgroups, v1: waves) a leapfrog launch over `boxes` writes.
 int leapfrog_blocks(const Layout& l, const LBox* boxes, int nbox, const LeapfrogTiling& t);
@@ -56,13 +47,6 @@ void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double
 // box = the whole global interior) and four distinct buffers (the redundant halo rows of step 1 read u^{n−1} that a
 // neighbouring wave may not yet have consumed, so nothing is overwritten in place). If `partials` is non-null the
 // error of u^{n+2} vs φ·ct2 is reduced per wave.
-struct Leapfrog2Tiling {
-  int rows = 2;           // output rows per wave (1, 2 or 4)
-  int occupancy = 0;      // rows = 2 only: >= 3 builds for 3 waves/SIMD (register cap, some spills)
-  int target_waves = 0;   // x-chunking target (0 = auto)
-  bool xcd_remap = true;
-  bool nt_store = true;
-};
 // [sx0, sx1): local x range where stage-1 (u^{n+1}) values are real; it extends one plane beyond `box` towards a
 // neighbouring rank of a slab decomposition (those ghost planes are recomputed redundantly from 2-deep halos).
 // Default (sx0 > sx1): this rank's updated region.
@@ -77,23 +61,6 @@ void launch_leapfrog2(const Layout& l, const Coeffs& c, const double* prev, cons
 // Error check of u^{n+k} when bit k−1 of `check_mask` is set (ct[k−1] = its time factor); stage k's partials go to
 // partials + (k−1)·level_stride (0: leapfrog_tb_partials(), the launch's block count). analytic_start: the pass starts at n = 1 from u⁰ = φ and u¹ computed in
 // the kernel (init_first's formulas, bit-identical), prev/cur are not read: it writes u^S, u^{S+1} with no HBM reads.
-constexpr int kTbTile = 32;  // (y, z) tile edge of the LDS S-step passes (leapfrog_tb_kernel.hpp tbk::kTile)
-struct LeapfrogTbTiling {
-  int stages = 4;         // steps per pass: 2..4 (k_leapfrog_tb), 2..5 (k_leapfrog_p2)
-  int threads = 1024;     // workgroup size (768 or 1024)
-  int init_threads = 768; // ... of the analytic-start pass (measured at 512³, S = 3: 768 → 932 µs, 1024 → 1027 µs;
-                          // the S = 4 passes go the other way: 768 → 1123 µs, 1024 → 1076 µs)
-  bool xcd_remap = true;  // (stores are always non-temporal: measured faster at every S)
-  bool xcd_blocks = false; // with xcd_remap: each XCD owns a square-ish tile block, not two-row strips (measured: no gain)
-  int target_blocks = 256; // fewer (y,z) tiles than this: split x into chunks (one workgroup per CU at 1 WG/CU)
-  int min_chunk = 16;      // ... of at least this many planes (each chunk recomputes S−1 planes on both sides)
-  bool p2 = true;          // the pair-tiled pass (k_leapfrog_p2, S ≤ 5) wherever it applies (leapfrog_p2_supported)
-  // (pair-tiled pass only) bit 0 / 1: also store u^{n+S−1} on the x ghost plane −1 / nx where a box starts / ends at
-  // the rank's first / last plane. The pass computes that plane anyway (level S−1 reaches one node beyond the box), so
-  // the slab exchange that follows sends S − 2 planes of u^{n+S−1} per face instead of S − 1 (solver_gpu.cpp
-  // ghost_bits). The 4-step k_leapfrog_tb refuses it.
-  int ghost_x1 = 0;
-};
 // Slab peer-push transport of an LDS pass (x faces only; every slab rank has the same plane geometry, so a plane's
 // in-plane offsets are the same on both sides). The pass
 //   * marches the upper face segment [x1 − T, x1) first, then [x0, x1 − T) (faces_first), so both face regions are
@@ -139,9 +106,6 @@ struct TbPack {
   int ny = 0, nz = 0;     // owned box
 };
 
-// Stage-real ranges of an LDS pass: per axis, where the intermediate levels hold real values (S−1 nodes into the
-// S-deep ghosts towards neighbouring ranks); lo > hi: the axis default (x: compute box, y/z: no restriction).
-inline LBox tb_default_real() { return LBox{1, 0, 1, 0, 1, 0}; }
 // Write back and invalidate every XCD's L2 (and the L1s): enough workgroups to reach every CU each run a system-scope
 // fence. Called once after allocating uncached buffers: lines of the same physical memory that a freed CACHED
 // allocation left dirty in some L2 would otherwise be evicted over the new buffer's contents later (measured: an
@@ -163,7 +127,6 @@ void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const double* prev, co
 // 2..4); no push / fused pack. launch_leapfrog_tb dispatches to it when tiling.p2 is set and it applies.
 // launch_leapfrog_p2_boxes: up to kP2MaxBoxes boxes in ONE launch (one grid, the x-chunk target shared by work), for the
 // overlapped schedules' shell boxes; their partials share one slot of `grid_blocks` entries.
-bool leapfrog_p2_supported(const Layout& l, const LBox& box, int stages);
 int leapfrog_p2_partials(const Layout& l, const LBox& box, const LeapfrogTbTiling& t);
 // (tests) the pair-tiled pass's thread → position table for S stages (kNT descriptors: (a+2) | (b+2)<<8 | lv<<16 |
 // kind<<20) and its geometry {E, HY, HZ, PZ, tile, LDS bytes at xlen 512 (pass, analytic start), max xlen (same)}
@@ -173,7 +136,6 @@ void launch_leapfrog_p2(const Layout& l, const Coeffs& c, const double* prev, co
                         double* out2, const LBox& box, const double* d_s, const double* ct, int check_mask,
                         Partial* partials, const LeapfrogTbTiling& t, hipStream_t stream, const LBox& real,
                         bool analytic_start, int level_stride = 0, int grid_blocks = 0);
-constexpr int kP2MaxBoxes = 6;  // boxes per pair-tiled launch (deep_split: up to 6 shells)
 void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
                               double* out2, const LBox* boxes, int nbox, const double* d_s, const double* ct,
                               int check_mask, Partial* partials, const LeapfrogTbTiling& t, hipStream_t stream,

@@ -21,6 +21,7 @@
 #include "wave3d/decomp.hpp"
 #include "wave3d/kernels.hpp"
 #include "wave3d/problem.hpp"
+#include "wave3d/schedule.hpp"
 
 namespace wave3d {
 
@@ -29,77 +30,6 @@ namespace wave3d {
     hipError_t _e = (expr);                                                                          \
     if (_e != hipSuccess) ::wave3d::fail(std::string(#expr) + ": " + hipGetErrorString(_e));          \
   } while (0)
-
-struct SolverOptions {
-  std::string decomp = "slab";  // slab | block | PxQxR
-  int check_every = 2;          // error check cadence (reference prints every 2nd step); 0 = only the last step
-  bool overlap = true;          // shell/interior split with the halo exchange on a side stream
-  bool graph = true;            // capture the whole solve into a hipGraph, replay it on every run()
-  bool timers = false;          // per-phase hipEvent timers (adds events to the stream; disables the graph)
-  bool debug_sync = false;      // hipDeviceSynchronize after every step (race triage; disables the graph)
-  bool poison_ghosts = false;   // NaN-fill ghost layers before each exchange (a missed halo poisons the errors)
-  bool fake_comm = false;       // perf study only: run rank `rank` of `world` alone, exchanges replaced by no-ops
-  bool fake_traffic = false;    // ... unless set: the exact message set goes to itself over a one-rank communicator
-                                // (RCCL copy kernels and bytes next to the passes; the received values are its own)
-  LeapfrogTiling tiling;
-  // Temporal blocking: up to `temporal` (2..5) steps per HBM pass wherever no halo exchange intervenes. One rank:
-  // k_leapfrog_p2 passes (pair-tiled, S ≤ 5; all levels in LDS, error checks at any level), the steps split into
-  // passes by measured per-step cost; slab and 3-D block ranks: the same passes with `temporal`-deep ghosts, one
-  // exchange per pass (the push transport: k_leapfrog_tb, S ≤ 4; tb = false: two-step k_leapfrog2 passes with 2-deep
-  // halos). 1 = one step per pass everywhere.
-  int temporal = 5;
-  bool tb = true;  // one rank: LDS kernel (false: k_leapfrog2 pairs, only where the intermediate step has no check)
-  Leapfrog2Tiling tiling2;
-  LeapfrogTbTiling tiling_tb;
-  // Start from u¹, u² computed analytically in one write-only pass (k_init_two) instead of u⁰, u¹ + a first step.
-  bool init2 = true;
-  // Slab ranks use the deep-halo fused schedule only from this many owned x-planes up (below, single steps are faster).
-  int deep_min_planes = 96;
-  // Slab ranks use the LDS multi-step passes (deep-tb) when every rank owns at least this many x-planes (and at least
-  // 2·temporal: each pass first computes the `steps` planes next to each neighbour, the shells that are sent).
-  int tb_min_planes = 16;
-  // Slab LDS passes (deep-tb) only: the "push" halo transport. Each pass stores the face planes its neighbours read as
-  // ghosts a second time, straight into their fine-grained staging over xGMI (TbPush, kernels.hpp): no exchange phase,
-  // no RCCL kernels competing for CUs, no shell launches; with `overlap` the pass produces both face regions first so
-  // the remote stores drain while it marches on. Cross-rank order: flags in uncached memory, raised at the end of a
-  // pass and waited for at the start of the next one (in the kernel; push_cp_wait: by the command processor with
-  // hipStreamWaitValue32 — eager launches only, for ranks that share one GPU). Peers are connected with
-  // connect_push() (multi-process: IPC handles) or by a GpuGroup.
-  bool push = false;
-  // Copy-engine ("sdma") transport (deep-tb slab and block ranks): the halo regions are copied into the neighbours'
-  // memory (IPC-mapped: their field buffers' ghost planes for slabs, their staging buffers for blocks) by
-  // hipMemcpyAsync(..., hipMemcpyDeviceToDeviceNoCU) on copy streams — the SDMA engines move them, no compute unit is
-  // taken from the LDS passes — and cross-rank order is kept by flag words in uncached device memory (waits: one-
-  // workgroup kernels; "arrived": a 4-byte copy-engine write behind the data). See transport_sdma.cpp for the protocol.
-  bool sdma = false;
-  // 3-D block LDS passes: the pass stores the z-face message parts of the next exchange straight into the send staging
-  // (TbPack, kernels.hpp); the pack kernel then copies only the x / y faces, edges and corners (A/B: --no-fused-pack)
-  bool fused_pack = true;
-  // slab LDS passes (deep-tb, pair-tiled kernel; RCCL / loopback / copy-engine transports): each pass also stores the
-  // u^{n+S−1} plane next to each neighbour face (it computes it anyway), so the exchange sends S planes of u^{n+S} and
-  // S − 2 (not S − 1) of u^{n+S−1} per face — 8 instead of 9 planes for a 5-step pass (A/B: --no-ghost-store)
-  bool ghost_store = true;
-  // deep-tb with overlap: the shell boxes run on the side stream concurrently with the interior (true), or on s0 before
-  // it (false: they get the whole GPU and finish first, so the exchange starts earlier — measured faster with the copy
-  // engines at 512³ and 2048³; concurrent helps the small block shells when no transfer follows; env W3D_SHELLS)
-  bool shells_concurrent = false;
-  // CUs kept free of the passes for RCCL's copy kernels (0: none). The compute stream gets a CU mask without the top
-  // `reserve_cus` CUs (KFD deals mask bits to the XCDs round-robin, so a multiple of 8 frees the same number of CUs in
-  // every XCD); a pass occupies a whole CU (LDS, VGPRs), so without a reserve RCCL's kernels of an overlapped exchange
-  // wait for the pass's last workgroups. The passes' x chunking then targets the remaining CUs. Env W3D_RESERVE_CUS.
-  int reserve_cus = 0;
-  // copy-engine transport: copy streams (each gets its own SDMA engine; 0 = auto: one per slab face, one for a block
-  // rank's messages — in a replayed graph a second copy stream made the 2048³ 2x2x2 rank slower, 48.8 vs 43.6 ms)
-  int sdma_streams = 0;
-  // copy-engine transport: bound of one in-kernel flag wait in seconds (0 = min(W3D_TIMEOUT_S / 2, 60)); the autotune
-  // sets a short one so a candidate whose peer is lost costs seconds, not minutes. It is baked into the captured
-  // graphs. Half the host's own wait bound by default, so the device reports the lost peer before the host gives up.
-  double flag_timeout_s = 0.0;
-  bool push_cp_wait = false;
-  // push ranks without an end-of-solve collective (no RCCL communicator): the flag epochs run on over the solves
-  // instead of being reset (eager launches: every launch carries its own epochs)
-  bool push_no_collective = false;
-};
 
 // Summed device time per phase of the last run() (SolverOptions::timers). compute = interior / whole-box / fused
 // passes; comm overlaps compute when the exchange runs on the side stream; gather is host wall time.
@@ -164,16 +94,17 @@ class GpuSolver {
 
   // One full solve: u⁰, u¹ → K−1 leapfrog steps with error checks → global error log on the host.
   RunResult run();
-  // n solves back to back (bench.py's timed block): a one-rank solver with a captured graph enqueues all n replays,
-  // each followed by the copy of its own error log into its slot of a pinned host buffer, and synchronises once at
-  // the end; the CLI then checks every timed solve's log against the warmup solve's. Every solve runs in full. (The
-  // host round trip it removes between solves measured within noise of 0 at 512³: profiles/r4/vmcnt/README.md.)
-  // Other solvers (several ranks, copy engines, push, timers, resume, no graph) call run() n times. solve_s: on the
-  // pipelined path the batch's wall time / n (RunResult::batched = true), otherwise each run()'s own time.
+  // n solves back to back (bench.py's timed block): a solver with a captured graph (one rank, RCCL ranks, fake ranks)
+  // enqueues all n replays, each followed by the gather (RCCL ranks: all-gather) and copy of its own error log into
+  // its slot of a pinned host buffer, and synchronises once at the end; the CLI then checks every timed solve's log
+  // against the warmup solve's. Every solve runs in full. (The host round trip it removes between solves measured
+  // within noise of 0 at 512³: profiles/r4/vmcnt/README.md.) Copy-engine, push, timers, resume and no-graph runs call
+  // run() n times. solve_s: on the pipelined path the batch's wall time / n (RunResult::batched = true), otherwise
+  // each run()'s own time.
   std::vector<RunResult> run_batch(int n);
   // Per-phase event timers for the following run() calls (those launch eagerly; the captured graph is kept for when
   // the timers are switched off again): a phase breakdown of exactly the schedule the graph replays.
-  void set_timers(bool on) { opt_.timers = on; }
+  void set_timers(bool on) { sch_.opt.timers = on; }
   // Loaded-field start (resume): every following run() starts at step n0 from u^{n0−1} = prev and
   // u^{n0} = cur (GLOBAL (N+1)³ C-order fields; each rank takes its box and all its ghost layers from them, so the
   // first pass needs no exchange) and continues the same schedule kinds to K, checking the steps after n0. The
@@ -188,51 +119,39 @@ class GpuSolver {
   unsigned long long field_hash(int which) const;
   int device() const { return dev_; }  // the HIP device this rank's buffers and streams live on
 
-  const Layout& layout() const { return lay_; }
-  const Dims& dims() const { return dims_; }
-  const HaloPlan& halo() const { return plan_; }
-  const Problem& problem() const { return prob_; }
-  const SolverOptions& options() const { return opt_; }
-  int rank() const { return rank_; }
-  int world() const { return world_; }
-  std::vector<LBox> shell_boxes() const { return shell_; }
-  LBox interior_box() const { return interior_; }
+  const Layout& layout() const { return sch_.lay; }
+  const Dims& dims() const { return sch_.dims; }
+  const HaloPlan& halo() const { return sch_.halo; }
+  const Problem& problem() const { return sch_.prob; }
+  const SolverOptions& options() const { return sch_.opt; }
+  int rank() const { return sch_.rank; }
+  int world() const { return sch_.world; }
+  std::vector<LBox> shell_boxes() const { return sch_.shell; }
+  LBox interior_box() const { return sch_.interior; }
   std::vector<int> check_steps() const;
   size_t device_bytes() const;
-  // "single-step" | "fused-single" (temporal blocking, one rank) | "deep-tb" (LDS multi-step passes, slab ranks)
-  // | "deep-halo" (two-step passes, slab ranks)
-  std::string mode() const;
+  // "single-step" | "fused-single" | "deep-tb" | "deep-tb-block" | "deep-halo" (RankSchedule::mode_name)
+  std::string mode() const { return sch_.mode_name(); }
   // push transport: this rank's staging + flag IPC handles (opaque bytes), and connecting to the neighbours from
   // every rank's handles (index = rank); GpuGroup ranks are connected in-process instead
-  bool push() const { return push_; }
+  bool push() const { return sch_.push; }
   std::string push_handles() const;
   void connect_push(const std::vector<std::string>& all);
   void connect_push_self();  // perf study (fake rank): forward into the own staging, wait for the own signals
   // copy-engine transport: this rank's IPC handles (field buffers, staging, flags) + layout facts, and connecting to
   // every neighbour from all ranks' handles (index = rank); a fake rank connects to itself
-  bool sdma() const { return sdma_; }
+  bool sdma() const { return sch_.sdma; }
   int copy_streams() const { return static_cast<int>(xcs_.size()); }
   std::string sdma_handles() const;
   void connect_sdma(const std::vector<std::string>& all);
   void connect_sdma_self();
-  // the halo overlap that actually runs: the exchange is issued on the side stream while the pass's interior runs
-  // (push: the passes produce their face planes first); false for schedules that exchange after the whole pass,
-  // whatever options().overlap says
-  bool overlapped() const {
-    if (!plan_.any() || world_ == 1) return false;
-    return push_ ? opt_.overlap : xstream() != s0_;
-  }
+  // the halo overlap that actually runs, whatever options().overlap says (RankSchedule::overlapped)
+  bool overlapped() const { return sch_.overlapped(); }
   // halo transport actually in use: "none" (one rank), "rccl", "push", "sdma", "fake" (perf study, no transport)
   std::string transport() const;
-  // Bytes one solve moves, from the unit schedule (SURVEY.md §5.5 effective GB/s). field_bytes: the compulsory
-  // device-memory traffic over the nodes this rank updates — a fused pass reads u^n, u^{n−1} and writes two levels,
-  // an analytic-start pass only writes its two, a single step reads two and writes one, the init kernel writes two;
-  // tile-halo re-reads that miss L2 are not in it (rocprof FETCH_SIZE counts those). halo_bytes: what this rank sends
-  // its neighbours per solve (RCCL / copy-engine messages, or the push transport's forwarded face planes).
-  struct Traffic {
-    double field_bytes = 0.0, halo_bytes = 0.0;
-  };
-  Traffic traffic();
+  // Bytes the last run() moved (schedule.hpp traffic; units_ is rebuilt at the start of every solve)
+  using Traffic = wave3d::Traffic;
+  Traffic traffic() const { return wave3d::traffic(sch_, units_, !analytic_ && resume_n_ == 0); }
 
  private:
   friend class GpuGroup;
@@ -247,83 +166,50 @@ class GpuSolver {
   void unpack_halo(hipStream_t st); // recv_buf_ → ghost layers
   void gather_errors(RunResult& r);
   void decode_log(const Partial* host, int nsrc, RunResult& r) const;  // per-rank partials → r's log (rank order)
-  // Schedule: a solve is phase_init() followed by units; a unit advances one step (in place over u^{n−1}) or 2..4
-  // (a fused pass into the two free buffers). Multi-rank units run shell -> exchange -> interior.
-  enum class Mode { kSingleStep, kFusedSingle, kDeep, kDeepTb };
-  struct Unit {
-    int n;      // current level u^n before the unit
-    int steps;  // 1: in-place single step; >= 2: one fused pass writing u^{n+steps−1}, u^{n+steps}
-    bool analytic = false;  // LDS pass from n = 1 computing u⁰, u¹ in the kernel (no init kernel, no reads)
-    bool fused() const { return steps >= 2; }
-  };
-  // one point-to-point message of an exchange: `tag` pairs it with the peer's matching message
-  struct Msg {
-    int peer, tag;
-    const double* send;
-    double* recv;
-    i64 count;
-  };
-  const Msg& peer_msg(const Msg& m, const std::vector<GpuSolver*>& ranks) const;
-  bool split() const;
-  bool post_exchange() const;  // the unit's NEW field is exchanged after its shell (else: current field, before)
-  // deep-tb without overlap: no shell launches; each pass runs whole and its faces are exchanged after it (on s0)
-  bool late_exchange() const;
-  bool needs_exchange(int i) const;
-  int ghost_bits(int i) const;  // x sides whose u^{n+S−1} ghost plane unit i's passes store (SolverOptions::ghost_store)
-  hipStream_t xstream() const;
-  bool pairable() const;
-  bool analytic_ok() const;  // the first unit can be an analytic-start LDS pass
-  void build_units();
-  void build_msgs(int i);
+  // The schedule (schedule.hpp) is decided once (sch_) and planned per solve (units_, in phase_init); the unit whose
+  // exchange is being issued is units_[cur_unit_]. A message's offsets become pointers where it is used: its field's
+  // buffer (uf: the two buffers the unit's pass writes), or the send / receive staging.
+  double* msg_buf(MsgField f, bool send, const int uf[2]) const;
+  const double* msg_send(const MsgPlan& m) const { return msg_buf(m.field, true, uf_) + m.send_off; }
+  double* msg_recv(const MsgPlan& m) const { return msg_buf(m.field, false, uf_) + m.recv_off; }
+  // (group ranks) the send region of the peer's message that pairs with m
+  const double* peer_send(const MsgPlan& m, const std::vector<GpuSolver*>& ranks) const;
+  bool needs_exchange(int i) const { return units_[static_cast<size_t>(i)].exchange; }
+  hipStream_t xstream() const { return sch_.side_stream() ? s1_ : s0_; }
   void phase_init();
   void unit_shell(int i);
   void unit_exchange_rccl(int i);
   void unit_interior(int i);
-  void tb_pass(const Unit& u, const LBox& box, int phase, hipStream_t st = nullptr);  // one k_leapfrog_tb launch
+  // What the LDS pass launches of unit u share: the tiling, time factors and check mask of its levels, its slot of
+  // partials (counted in tb_slots_ when a level is checked) and the stage-real ranges.
+  struct TbArgs {
+    LeapfrogTbTiling t;
+    double cts[5] = {0, 0, 0, 0, 0};
+    int mask = 0, slots = 1;
+    Partial* part = nullptr;
+    LBox real;
+  };
+  TbArgs tb_args(const UnitPlan& u);
+  void tb_pass(const UnitPlan& u, const LBox& box, int phase, hipStream_t st = nullptr);  // one k_leapfrog_tb launch
   // the unit's shell boxes in ONE pair-tiled launch when that applies (returns false: launch them one by one)
-  bool tb_pass_boxes(const Unit& u, const std::vector<LBox>& boxes, int phase, hipStream_t st);
-  // deep-tb with overlap: unit i's shell boxes (what the neighbours receive, computed first) and the interior box
-  void tb_split(int i, std::vector<LBox>& shells, LBox& interior) const;
-  std::vector<LBox> tb_shells(int i) const;
-  LBox tb_interior(int i) const;
+  bool tb_pass_boxes(const UnitPlan& u, const std::vector<LBox>& boxes, int phase, hipStream_t st);
   // in-process group steps (GpuGroup): pack own faces → (group barrier) → pull peers' faces → (group barrier)
   void lb_pack(int i);
   void lb_pull(int i, const std::vector<GpuSolver*>& ranks, hipEvent_t all_packed);
   void lb_fence(int i, hipEvent_t all_pulled);
 
-  Problem prob_;
-  SolverOptions opt_;
+  RankSchedule sch_;
   Coeffs coef_;
   int dev_ = 0;
-  int rank_, world_;
   std::shared_ptr<Comm> comm_;
   bool loopback_ = false;
-  Dims dims_;
-  Layout lay_;
-  HaloPlan plan_;
-  std::vector<LBox> shell_;
-  LBox interior_;
-  LBox full_;
 
   double* u_[4] = {nullptr, nullptr, nullptr, nullptr};  // [2], [3] only with temporal blocking
-  int nbuf_ = 2;
-  Mode mode_ = Mode::kSingleStep;
-  std::vector<Unit> units_;
-  std::vector<Msg> msgs_;
+  std::vector<UnitPlan> units_;
   int uf_[2] = {2, 3};            // output buffers of the current fused unit
-  std::vector<LBox> dshell_;      // deep mode: output x-slabs next to neighbours (shell) ...
-  LBox dint_;                     // ... and the rest (interior)
-  i64 sx0_ = 0, sx1_ = 0;         // deep mode: stage-1 x range (one ghost plane beyond each neighbour face)
-  LBox sreal_;                    // deep-tb: stage-real ranges per axis (temporal − 1 nodes into each neighbour's ghosts)
-  bool block_tb_ = false;         // deep-tb on a 3-D block decomposition (S-deep ghosts on every split axis)
-  DeepPlan deep_[6];              // block_tb_: exchange plan before a pass of s steps (index s = 2..temporal)
-  BoxCopyTable pack_tab_[6], unpack_tab_[6];  // ... and its device job tables (send / receive regions)
+  BoxCopyTable pack_tab_[6], unpack_tab_[6];  // block_tb: device job tables of sch_.deep[] (send / receive regions)
   TbPack pk_host_[6];                          // fused z-face pack per exchange depth (fused_pack; w = 0: none)
   TbPack* pk_dev_ = nullptr;                   // ... the same five entries in device memory
-  i64 deep_max_ = 0;              // largest staging buffer of those plans (doubles): the receive staging
-  i64 sbase_[6] = {};             // send staging: the region of depth s starts at sbase_[s] (one region per depth)
-  i64 send_total_ = 0;            // ... and its size (doubles)
-  int deep_s_ = 2;                // depth of the exchange being issued
   std::vector<int> n_dshell_;     // partials per deep shell launch
   int n_dint_ = 0;
   int prev_buf_ = 1;             // buffer index holding u^{K−1} after a solve
@@ -347,13 +233,11 @@ class GpuSolver {
   // LDS passes: each unit's partials go to region tb_region_ of kTbRegions; their reductions are queued and issued as
   // one batched launch when the regions wrap and at the end of the solve (one launch instead of one per checked step)
   static constexpr int kTbRegions = 8;
-  static constexpr int kTbSlots = 8;  // launches with partials per level and unit (shell boxes + interior)
   static constexpr int kTbLevels = 5; // levels per pass (5-step passes: k_leapfrog_p2)
   Partial* tb_partials_ = nullptr;
   int tb_region_ = 0;
   std::vector<ReduceJob> pending_;
   void flush_reduces();
-  bool nb_lo_ = false, nb_hi_ = false;                      // x neighbours (slab ranks)
   int cur_ = 1, old_ = 0;                     // buffer roles during enqueue
   int start_n_ = 1;                           // first leapfrog step after the init kernel
   bool analytic_ = false;                     // the first unit computes u⁰, u¹ itself (no init kernel)
@@ -376,9 +260,9 @@ class GpuSolver {
   template <class F>
   void timed(int phase, hipStream_t st, F&& f);
   void collect_phases(RunResult& r);
-  void poison(hipStream_t st);
+  // --poison-ghosts: NaN into the ghost regions u's exchange fills (uf: the buffers u's pass writes)
+  void poison(const UnitPlan& u, const int uf[2], hipStream_t st);
   // push transport (slab deep-tb)
-  bool push_ = false;
   double* stg_ = nullptr;       // [parity][field (0: u^{n+S−1}, 1: u^{n+S})][side (0: lo ghosts, 1: hi)][T planes]
   unsigned* flags_ = nullptr;   // uncached: [0] raised by the lower neighbour, [1] by the upper, [4] timeout, [8] done
   double* peer_stg_[2] = {nullptr, nullptr};   // neighbours' staging (lo, hi)
@@ -390,27 +274,19 @@ class GpuSolver {
   TbPush* push_dev_ = nullptr;                 // ... to this device table the passes read
   TbPush make_push(int j, int npass) const;    // pass j (1-based) of npass
   mutable unsigned push_uid_ = 0;              // solver instance number (table tags)
-  i64 stg_off(int par, int field, int side) const { return ((par * 2 + field) * 2 + side) * lay_.xg * lay_.plane; }
+  i64 stg_off(int par, int field, int side) const { return ((par * 2 + field) * 2 + side) * sch_.lay.xg * sch_.lay.plane; }
   void connect_push_peer(int side, double* stg, unsigned* flags, bool ipc);
   void push_finish(hipStream_t st);  // end of a solve: zero this rank's flags (after its last wait)
   void push_check();                 // after a solve: fail if a wait timed out
-  // copy-engine transport (transport_sdma.cpp). Link k = one neighbour: slab ranks [lo, hi] (faces that exist),
-  // block ranks the peers of deep_[] in direction order. This rank's flag words: [2k] "arrived" (link k's copies into
-  // this rank are complete), [2k + 1] "done" (link k has consumed this rank's previous message and finished the pass
-  // that read the regions the next message overwrites).
-  struct XLink {
-    int peer = -1;
-    int side = 0;                  // slab: 0 = lower neighbour, 1 = upper
-    int slot = 0;                  // this rank's link index in the PEER's flags
+  // copy-engine transport (transport_sdma.cpp). Link k = one neighbour (schedule.hpp LinkPlan). This rank's flag
+  // words: [2k] "arrived" (link k's copies into this rank are complete), [2k + 1] "done" (link k has consumed this
+  // rank's previous message and finished the pass that read the regions the next message overwrites).
+  struct XLink : LinkPlan {
     unsigned* flags = nullptr;     // the peer's flag words (IPC-mapped, or this rank's own for a fake rank)
     double* u[4] = {nullptr, nullptr, nullptr, nullptr};  // slab: the peer's field buffers
     double* recv = nullptr;        // block: the peer's receive staging
-    i64 peer_nx = 0;               // slab: the peer's owned planes
-    i64 recv_off[6] = {0, 0, 0, 0, 0, 0};  // block: offset of this rank's message in the peer's staging, per depth
-                                           // s = 2..5 (indexed by s, like deep_[] and sbase_[])
     bool ipc = false;              // mapped with hipIpcOpenMemHandle (closed in the destructor)
   };
-  bool sdma_ = false;
   std::vector<XLink> xlinks_;
   unsigned* xflags_ = nullptr;     // uncached: 2 words per link
   int xpar_ = 0;                   // parity of the solve being enqueued (flag values alternate between two sets)
@@ -428,12 +304,10 @@ class GpuSolver {
   unsigned xval(int i) const { return (xpar_ ? 0x10000u : 0u) + static_cast<unsigned>(i + 1); }
   unsigned xend(int par) const { return (par ? 0x10000u : 0u) + 0xFFFFu; }
   void sdma_alloc();
-  std::vector<XLink> sdma_links() const;  // link geometry (peer, side, slot) without pointers
   unsigned* xsig(const XLink& l, int word) const { return l.flags + 2 * l.slot + word; }
   void unit_exchange_sdma(int i);  // side stream after unit i's shells (or s0 after the pass): copies + "arrived"
   void sdma_receive(int i);        // s0 before unit i ≥ 1: wait "arrived" (i − 1), unpack, signal "done" (i − 1)
   void sdma_finish();              // s0 after the last unit: "done" for the next solve's first exchange
-  void sdma_poison(int i, const int uf[2]);  // --poison-ghosts: NaN into the regions exchange i fills
   unsigned long long flag_ticks() const;     // bound of one in-kernel flag wait (wall-clock ticks)
   // every link has the peer pointers its copies and signals use (connect_sdma / connect_sdma_self / a group): a
   // solver used unconnected would make the copy engines and k_flag_sync write through null + offset (a GPU fault)
@@ -445,7 +319,7 @@ class GpuSolver {
 // also a roctx range ("w3d:<phase>:u<unit>"), so rocprofv3 --marker-trace timelines show the schedule.
 template <class F>
 void GpuSolver::timed(int phase, hipStream_t st, F&& f) {
-  if (!opt_.timers) {
+  if (!sch_.opt.timers) {
     f();
     return;
   }

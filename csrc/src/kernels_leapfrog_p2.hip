@@ -224,18 +224,6 @@ unsigned long long* wgtime_slot(int nblocks, int S, bool init) {
 
 }  // namespace
 
-bool leapfrog_p2_supported(const Layout& l, const LBox& box, int stages) {
-  // any box inside the rank's compute range in y/z (the whole range: one rank, x slabs, a 3-D block's whole box; or a
-  // sub-box: the overlapped block schedule's shells and interior, cpu.hpp deep_split) whose pairs start on 16-byte
-  // nodes and which ends on a whole pair unless it ends at the rank's last node: the pass stores whole pairs, so a box
-  // ending in the middle of a pair would also write the first node of the next box (beyond the rank's last node the
-  // second node of a pair is a ghost, which the next exchange rewrites)
-  const LBox full = compute_box(l);
-  return stages >= 2 && stages <= 5 && l.yg >= 1 && l.zg >= 1 && box.y0 >= full.y0 && box.y1 <= full.y1 &&
-         box.z0 >= full.z0 && box.z1 <= full.z1 && (box.z0 + l.zg + l.zs) % 2 == 0 &&
-         (box.z1 == full.z1 || (box.z1 - box.z0) % 2 == 0);
-}
-
 int leapfrog_p2_partials(const Layout& l, const LBox& box, const LeapfrogTbTiling& t) {
   // (the largest block count over S = 2..5: the chunk length shrinks with S, whose levels share the LDS with the
   // chunk's x sin table — ADVICE r5: S = 2 alone undercounted boxes longer than the S = 5 chunk)

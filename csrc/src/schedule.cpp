@@ -1,0 +1,355 @@
+// The host-side solve schedule. See wave3d/schedule.hpp.
+#include "wave3d/schedule.hpp"
+
+#include <algorithm>
+
+namespace wave3d {
+
+namespace {
+
+// 5-step passes exist only in the pair-tiled kernel (k_leapfrog_p2): temporal 5 becomes 4 when that kernel is off
+// (tb or tiling_tb.p2 unset), and on several ranks unless they run deep-tb on a transport other than push (whose
+// forwarding stores are k_leapfrog_tb's, S ≤ 4). (3-D blocks, overlapped or not, keep 5: the overlapped schedule's
+// shell and interior boxes are cut on whole pairs, cpu.hpp deep_split.)
+int clamp_temporal(const SolverOptions& o, int world, bool deep_tb) {
+  const bool five = o.tb && o.tiling_tb.p2 && (world == 1 || (deep_tb && !o.push));
+  return o.temporal == 5 && !five ? 4 : o.temporal;
+}
+
+// Deep-halo fused passes need every unit to be a pair with no error check on its intermediate step, starting from the
+// analytic (u¹, u²): K even and no odd check step below K.
+bool pairable(const RankSchedule& s) {
+  const int K = s.prob.K;
+  if (!s.opt.init2 || K < 4 || (K - 2) % 2 != 0) return false;
+  for (int n = 3; n < K; n += 2)
+    if (s.is_check(n)) return false;
+  return true;
+}
+
+}  // namespace
+
+std::string RankSchedule::mode_name() const {
+  switch (mode) {
+    case Mode::kFusedSingle: return "fused-single";
+    case Mode::kDeep: return "deep-halo";
+    case Mode::kDeepTb: return block_tb ? "deep-tb-block" : "deep-tb";
+    default: return "single-step";
+  }
+}
+
+// (u¹ is the pass's input level: it cannot carry a check)
+bool RankSchedule::analytic_ok() const { return opt.tb && opt.init2 && opt.temporal >= 2 && prob.K >= 3 && !is_check(1); }
+
+RankSchedule make_rank_schedule(const Problem& prob, const SolverOptions& opt, int rank, int world,
+                                double free_device_bytes) {
+  RankSchedule s;
+  s.prob = prob;
+  s.opt = opt;
+  s.rank = rank;
+  s.world = world;
+  W3D_REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank/world");
+  W3D_REQUIRE(!(opt.push && opt.sdma), "push and sdma are two different transports");
+  W3D_REQUIRE(opt.temporal >= 1 && opt.temporal <= 5, "temporal must be 1..5");
+  s.dims = parse_dims(opt.decomp, world, prob.N);
+  const Box box = rank_box(prob, s.dims, rank);
+  W3D_REQUIRE(box.nx() >= 1 && box.ny() >= 1 && box.nz() >= 1,
+              "decomposition leaves a rank without nodes; use fewer ranks or a larger N");
+  // schedule mode: temporal blocking on one rank, or on a 1-D slab decomposition with `temporal`-deep x halos (LDS
+  // passes) or 2-deep ones (two-step passes).
+  const Dims& d = s.dims;
+  const bool slab = d.py == 1 && d.pz == 1;
+  s.opt.temporal = clamp_temporal(opt, world, true);  // (the pass depth if this world gets deep-tb)
+  if (s.opt.temporal >= 2 && world == 1) s.mode = Mode::kFusedSingle;
+  if (s.opt.temporal >= 2 && world > 1) {
+    // smallest extent of any rank along each axis (every rank must be able to feed its neighbours' deep halos)
+    i64 mn[3] = {box.nx(), box.ny(), box.nz()};
+    for (int r = 0; r < world; ++r) {
+      const Box b = rank_box(prob, d, r);
+      mn[0] = imin(mn[0], b.nx());
+      mn[1] = imin(mn[1], b.ny());
+      mn[2] = imin(mn[2], b.nz());
+    }
+    const int rem = prob.K - (s.analytic_ok() ? 1 : 2);  // steps left to the passes (each takes 2..temporal)
+    const i64 T2 = 2 * s.opt.temporal;
+    // 3-D blocks: S-deep ghosts on every split axis, one exchange (faces, edges, corners) between passes
+    const bool block_fits = (d.px == 1 || mn[0] >= imax(T2, 8)) && (d.py == 1 || mn[1] >= imax(T2, 8)) &&
+                            (d.pz == 1 || mn[2] >= imax(T2, 8));
+    if (opt.tb && opt.init2 && rem >= 2 && (slab ? mn[0] >= imax(opt.tb_min_planes, T2) : block_fits))
+      s.mode = Mode::kDeepTb;
+    // (two-step passes, measured with --fake-rank on 512³: they win from ~128 local planes up, but at 64 planes the
+    // two 2-plane shell passes and the per-chunk stage-1 recompute cost more than the saved traffic)
+    else if (slab && mn[0] >= opt.deep_min_planes && mn[0] >= 3 && pairable(s))
+      s.mode = Mode::kDeep;
+  }
+  s.block_tb = s.mode == Mode::kDeepTb && !slab;
+  s.opt.temporal = clamp_temporal(opt, world, s.mode == Mode::kDeepTb);
+  // (the fused z-face pack lives in k_leapfrog_tb: with the pair-tiled pass the pack kernel packs the z faces too)
+  if (s.block_tb && opt.tiling_tb.p2) s.opt.fused_pack = false;
+  if (opt.push && world > 1) {
+    W3D_REQUIRE(s.mode == Mode::kDeepTb && !s.block_tb,
+                "push transport: slab LDS passes (deep-tb) only, not " + s.mode_name());
+    s.push = true;
+  }
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    const i64 T = s.opt.temporal;
+    s.lay = make_layout(prob, box, 16, s.mode == Mode::kDeep ? 2 : (s.mode == Mode::kDeepTb && d.px > 1) ? T : 1,
+                        s.block_tb && d.py > 1 ? T : 1, s.block_tb && d.pz > 1 ? T : 1);
+    // memory plan: temporal blocking needs four field buffers; fall back to the two-buffer in-place scheme when four
+    // do not fit next to the other allocations (2049³ fp64 is 68.8 GB per buffer)
+    const double need2 = 2.0 * static_cast<double>(s.lay.bytes()), headroom = 2.0e9;
+    if (s.mode != Mode::kSingleStep && 2.0 * need2 + headroom > free_device_bytes) {
+      W3D_REQUIRE(!s.push, "push transport: four field buffers do not fit");
+      s.mode = Mode::kSingleStep;
+      s.block_tb = false;
+      continue;
+    }
+    W3D_REQUIRE(need2 + 1.0e8 < free_device_bytes,
+                "not enough device memory for two field buffers of " + std::to_string(s.lay.bytes()) + " bytes");
+    break;
+  }
+  s.nbuf = s.mode == Mode::kSingleStep ? 2 : 4;
+  if (opt.sdma && world > 1) {
+    W3D_REQUIRE(s.mode == Mode::kDeepTb,
+                "sdma transport: LDS multi-step passes (deep-tb, slab or block) only, not " + s.mode_name());
+    s.sdma = true;
+  }
+  // (stream memops are not captured into graphs, running epochs are per-launch arguments; timers and the per-step
+  // synchronisation need eager launches)
+  if ((s.push && (opt.push_cp_wait || opt.push_no_collective)) || opt.timers || opt.debug_sync) s.opt.graph = false;
+  s.halo = make_halo_plan(s.lay, d, rank);
+  s.full = compute_box(s.lay);
+
+  // interior = compute box minus one layer on every side that has a neighbour; shell = the rest (cpu.hpp shell_split)
+  for (int a = 0; a < 3; ++a)
+    for (int sd = 0; sd < 2; ++sd) s.nb[a][sd] = neighbor_rank(d, rank, a, sd) >= 0;
+  const auto& nb = s.nb;
+  const LBox& full = s.full;
+  shell_split(full, nb, s.shell, s.interior);
+
+  // deep-halo slab: the 2 owned planes next to each neighbour are the shell (they are what the neighbours receive);
+  // stage-1 values are real one ghost plane beyond each neighbour face
+  if (s.mode == Mode::kDeep) {
+    i64 lo = full.x0, hi = full.x1;
+    if (nb[0][0]) {
+      const i64 e = imin(full.x0 + 2, full.x1);
+      s.dshell.push_back(LBox{full.x0, e, full.y0, full.y1, full.z0, full.z1});
+      lo = e;
+    }
+    if (nb[0][1]) {
+      const i64 b = imax(full.x1 - 2, lo);
+      if (b < full.x1) s.dshell.push_back(LBox{b, full.x1, full.y0, full.y1, full.z0, full.z1});
+      hi = b;
+    }
+    s.dint = hi > lo ? LBox{lo, hi, full.y0, full.y1, full.z0, full.z1} : LBox{};
+    s.sx0 = full.x0 - (nb[0][0] ? 1 : 0);
+    s.sx1 = full.x1 + (nb[0][1] ? 1 : 0);
+  }
+  // deep-tb: stage values are real up to temporal − 1 nodes beyond each neighbour face (recomputed from the
+  // temporal-deep halo); the shell/interior split depends on the next pass's depth and is made per unit
+  if (s.mode == Mode::kDeepTb) {
+    const i64 T1 = s.opt.temporal - 1;
+    s.sx0 = full.x0 - (nb[0][0] ? T1 : 0);
+    s.sx1 = full.x1 + (nb[0][1] ? T1 : 0);
+    s.sreal = LBox{s.sx0, s.sx1, full.y0 - (nb[1][0] ? T1 : 0), full.y1 + (nb[1][1] ? T1 : 0),
+                   full.z0 - (nb[2][0] ? T1 : 0), full.z1 + (nb[2][1] ? T1 : 0)};
+  }
+  // 3-D block passes: one plan per pass depth that can follow an exchange. The send staging holds one region per depth
+  // (sbase): the fused z-face pack writes only the real nodes of its message parts and leaves the global-boundary
+  // entries at their initial zero, which a region shared with the messages of another depth (whose parts land at other
+  // offsets) would overwrite — measured: a depth-3 exchange followed by a depth-4 one sent the depth-3 values of those
+  // entries as boundary ghosts
+  for (int st = 2; st <= s.opt.temporal && s.block_tb; ++st) {
+    s.deep[st] = make_deep_plan(s.lay, d, rank, st);
+    s.deep_max = imax(s.deep_max, s.deep[st].total);
+    s.sbase[st] = s.send_total;
+    s.send_total += round_up(s.deep[st].total, 32);
+  }
+  return s;
+}
+
+namespace {
+
+// Split the steps start_n..K into passes of 1..temporal steps minimising the summed cost: µs per step of a pass of s
+// steps with every 2nd level checked, measured at 512³ (tools/tune_leapfrog.py --tb); the analytic first pass reads
+// nothing but computes u⁰, u¹ (compute-bound). Slab and block ranks (deep-tb) take passes of ≥ 2 steps only: every
+// pass writes the two levels the next one reads, so each exchange is one message pair per face.
+void plan_passes(const RankSchedule& s, int n, bool analytic, std::vector<UnitPlan>& units) {
+  static const double kStepCostTb[6] = {0.0, 610.0, 437.0, 302.0, 258.0, 1e9};
+  // (analytic: φ-stage start, re-measured)
+  static const double kAnalyticCostTb[6] = {0.0, 1e9, 346.0, 300.0, 318.0, 1e9};
+  // the pair-tiled passes (k_leapfrog_p2, one rank): µs per step at 512³ (profiles/r5/)
+  static const double kStepCostP2[6] = {0.0, 610.0, 430.0, 290.0, 225.0, 180.0};
+  static const double kAnalyticCostP2[6] = {0.0, 1e9, 300.0, 200.0, 135.0, 1e9};
+  // (slab ranks and 3-D block ranks too: their shell / interior boxes are cut on whole pairs)
+  const bool p2 = s.opt.tiling_tb.p2 && !s.push && leapfrog_p2_supported(s.lay, s.full, 2);
+  const double* kStepCost = p2 ? kStepCostP2 : kStepCostTb;
+  const double* kAnalyticCost = p2 ? kAnalyticCostP2 : kAnalyticCostTb;
+  const int K = s.prob.K, rem = K - n, smax = s.opt.temporal, smin = s.mode == Mode::kDeepTb ? 2 : 1;
+  std::vector<double> best(static_cast<size_t>(rem + 1), 1e300);
+  std::vector<int> take(static_cast<size_t>(rem + 1), 1);
+  best[0] = 0.0;
+  for (int r = 1; r <= rem; ++r)
+    for (int st = smin; st <= std::min(smax, r); ++st) {
+      const double c = best[static_cast<size_t>(r - st)] + st * kStepCost[st];
+      if (c < best[static_cast<size_t>(r)]) {
+        best[static_cast<size_t>(r)] = c;
+        take[static_cast<size_t>(r)] = st;
+      }
+    }
+  if (analytic) {
+    // the analytic first pass takes 2..temporal steps: minimise its cost plus the best split of the rest
+    int bf = 2;
+    double bc = 1e300;
+    for (int f = 2; f <= std::min(smax, rem); ++f) {
+      const double c = f * kAnalyticCost[f] + best[static_cast<size_t>(rem - f)];
+      if (c < bc) {
+        bc = c;
+        bf = f;
+      }
+    }
+    units.push_back(UnitPlan{n, bf, true});
+    n += bf;
+  }
+  W3D_REQUIRE(best[static_cast<size_t>(K - n)] < 1e299, "no pass schedule for the remaining steps");
+  for (int r = K - n; r > 0; r -= take[static_cast<size_t>(r)]) {
+    units.push_back(UnitPlan{n, take[static_cast<size_t>(r)]});
+    n += take[static_cast<size_t>(r)];
+  }
+}
+
+// The messages of unit u's exchange, which a pass of `u.depth` steps follows (deep modes).
+void plan_msgs(const RankSchedule& s, UnitPlan& u) {
+  const Layout& l = s.lay;
+  const i64 P = l.plane, nx = l.nx;
+  if (s.block_tb) {
+    // one packed message per neighbour (faces, edges, corners): u^{n+S} s deep, then u^{n+S−1} s − 1 deep
+    for (const DeepPeer& q : s.deep[u.depth].peers)
+      u.msgs.push_back(MsgPlan{q.peer, 0, MsgField::kStaging, s.sbase[u.depth] + q.buf_off, q.buf_off, q.count});
+    return;
+  }
+  for (const Face& f : s.halo.faces) {
+    if (s.mode == Mode::kDeepTb || s.mode == Mode::kDeep) {
+      // the next pass of w steps reads u^{n+S} (this pass's out2) on w ghost planes and u^{n+S−1} (out1) on w − 1
+      // (deep-halo: 2 and 1). ghost_bits: the pass stored u^{n+S−1} on the first ghost plane itself; that part then
+      // starts one plane further from the face on both ends: our planes 1..w−2 / nx−w+1..nx−2 into the peer's ghosts
+      // at distance 2..w−1
+      W3D_REQUIRE(f.axis == 0, "deep-tb and deep-halo modes are slab-only");
+      const i64 w = s.mode == Mode::kDeep ? 2 : u.depth, g = (u.ghost_bits >> f.side) & 1, d1 = w - 1 - g;
+      const i64 s2 = f.side == 0 ? 0 : nx - w, s1 = f.side == 0 ? g : nx - (w - 1);
+      const i64 r2 = f.side == 0 ? -w : nx, r1 = f.side == 0 ? -(w - 1) : nx + g;
+      u.msgs.push_back(MsgPlan{f.peer, 0, MsgField::kOut2, l.plane_off(s2), l.plane_off(r2), w * P});
+      if (d1 > 0) u.msgs.push_back(MsgPlan{f.peer, 1, MsgField::kOut1, l.plane_off(s1), l.plane_off(r1), d1 * P});
+    } else if (f.contiguous) {
+      u.msgs.push_back(MsgPlan{f.peer, 0, MsgField::kCurrent, f.send_off, f.recv_off, f.count});
+    } else {
+      u.msgs.push_back(MsgPlan{f.peer, 0, MsgField::kStaging, f.pack_off, f.pack_off, f.count});
+    }
+  }
+}
+
+}  // namespace
+
+std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic) {
+  std::vector<UnitPlan> units;
+  const int K = s.prob.K;
+  int n = start_n;
+  if ((s.mode == Mode::kFusedSingle && s.opt.tb) || s.mode == Mode::kDeepTb) {
+    plan_passes(s, n, analytic, units);
+  } else if (s.mode == Mode::kFusedSingle) {
+    while (n <= K - 1) {
+      const bool f = n + 2 <= K && !s.is_check(n + 1);
+      units.push_back(UnitPlan{n, f ? 2 : 1});
+      n += f ? 2 : 1;
+    }
+  } else {
+    const int st = s.mode == Mode::kDeep ? 2 : 1;
+    for (; n <= K - 1; n += st) units.push_back(UnitPlan{n, st});
+  }
+  const int nu = static_cast<int>(units.size());
+  const bool tb = s.mode == Mode::kDeepTb;
+  for (int i = 0; i < nu; ++i) {
+    UnitPlan& u = units[static_cast<size_t>(i)];
+    u.interior = s.full;
+    // (push: the passes deliver the ghosts themselves)
+    u.exchange = s.halo.any() && !s.push && (s.post_exchange() ? i + 1 < nu : i > 0);
+    if (!u.exchange) continue;
+    if (tb) u.depth = units[static_cast<size_t>(i) + 1].steps;
+    if (tb && s.opt.ghost_store && !s.block_tb && s.opt.tiling_tb.p2 && !(u.analytic && u.steps > 4) &&
+        leapfrog_p2_supported(s.lay, s.full, u.steps))
+      for (const Face& f : s.halo.faces)
+        if (f.axis == 0) u.ghost_bits |= 1 << f.side;
+    plan_msgs(s, u);
+    if (tb && !s.late_exchange()) {
+      deep_split(s.full, s.nb, u.depth, kTbTile, u.shells, u.interior);
+      W3D_REQUIRE(static_cast<int>(u.shells.size()) < kTbSlots, "deep-tb: too many shell boxes");
+    }
+  }
+  return units;
+}
+
+std::vector<LinkPlan> plan_links(const RankSchedule& s) {
+  std::vector<LinkPlan> v;
+  if (!s.block_tb) {
+    for (int side = 0; side < 2; ++side) {
+      const int peer = neighbor_rank(s.dims, s.rank, 0, side);
+      if (peer < 0) continue;
+      LinkPlan l;
+      l.peer = peer;
+      l.side = side;
+      // the peer's links are [its lower neighbour (if any), its upper]: this rank is the peer's upper neighbour when
+      // the peer is below it
+      l.slot = side == 0 ? (neighbor_rank(s.dims, peer, 0, 0) >= 0 ? 1 : 0) : 0;
+      l.peer_nx = rank_box(s.prob, s.dims, peer).nx();
+      v.push_back(l);
+    }
+    return v;
+  }
+  for (const DeepPeer& q : s.deep[2].peers) {
+    LinkPlan l;
+    l.peer = q.peer;
+    // the peer's plan (its layout has the same ghost depths): this rank's index among its peers, and where its message
+    // lands in the peer's staging for every pass depth
+    const Layout pl = make_layout(s.prob, rank_box(s.prob, s.dims, q.peer), 16, s.lay.xg, s.lay.yg, s.lay.zg);
+    W3D_REQUIRE(s.opt.temporal < static_cast<int>(sizeof(l.recv_off) / sizeof(l.recv_off[0])),
+                "sdma: pass depth beyond the link's offset table");
+    for (int st = 2; st <= s.opt.temporal; ++st) {
+      const DeepPlan pp = make_deep_plan(pl, s.dims, q.peer, st);
+      int idx = -1;
+      for (size_t k = 0; k < pp.peers.size(); ++k)
+        if (pp.peers[k].peer == s.rank) idx = static_cast<int>(k);
+      W3D_REQUIRE(idx >= 0, "sdma: peer plan does not list this rank");
+      const DeepPeer& back = pp.peers[static_cast<size_t>(idx)];
+      const DeepPeer* mine = nullptr;
+      for (const DeepPeer& m : s.deep[st].peers)
+        if (m.peer == q.peer) mine = &m;
+      W3D_REQUIRE(mine && mine->count == back.count, "sdma: message sizes differ between the two ends of a link");
+      l.slot = idx;
+      l.recv_off[st] = back.buf_off;
+    }
+    v.push_back(l);
+  }
+  return v;
+}
+
+Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool init_kernel) {
+  Traffic t;
+  const Layout& l = s.lay;
+  const double plane_bytes = static_cast<double>(l.plane) * sizeof(double);
+  const double node_bytes = static_cast<double>(l.cx1 - l.cx0) * static_cast<double>(l.cy1 - l.cy0) *
+                            static_cast<double>(l.cz1 - l.cz0) * sizeof(double);
+  if (init_kernel) t.field_bytes += 2.0 * node_bytes;  // init kernel: u¹, u² (or u⁰, u¹)
+  for (const UnitPlan& u : units) {
+    t.field_bytes += node_bytes * (u.analytic ? 2.0 : u.fused() ? 4.0 : 3.0);
+    // (the stored u^{n+S−1} ghost planes: one plane per face)
+    t.field_bytes += static_cast<double>((u.ghost_bits & 1) + (u.ghost_bits >> 1)) * plane_bytes;
+    for (const MsgPlan& m : u.msgs) t.halo_bytes += static_cast<double>(m.count) * sizeof(double);
+  }
+  if (s.push) {  // each pass but the last forwards T planes of u^{n+S} and T − 1 of u^{n+S−1} per face
+    const double T = static_cast<double>(l.xg);
+    t.halo_bytes = static_cast<double>(s.halo.faces.size()) * (2.0 * T - 1.0) * plane_bytes *
+                   static_cast<double>(units.empty() ? 0 : units.size() - 1);
+  }
+  return t;
+}
+
+}  // namespace wave3d

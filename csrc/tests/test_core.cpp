@@ -1,4 +1,5 @@
-// Native unit tests of the host-side core (no GPU): decomposition, layout, halo plans, scheme, CPU solver.
+// Native unit tests of the host-side core (no GPU): decomposition, layout, halo plans, scheme, CPU solver, and the
+// solve schedule (schedule.hpp: modes, unit lists, messages, shell boxes, traffic).
 //
 // SURVEY.md §4.2 "unit (C++/ctest)": exact-arithmetic checks of the pieces every backend shares. Built and run by
 // CMake/ctest (CMakeLists.txt) and, with host AddressSanitizer + UBSan, by tests/test_native_unit.py.
@@ -13,6 +14,7 @@
 #include "wave3d/cpu.hpp"
 #include "wave3d/decomp.hpp"
 #include "wave3d/problem.hpp"
+#include "wave3d/schedule.hpp"
 #include "wave3d/stencil.hpp"
 
 using namespace wave3d;
@@ -223,6 +225,265 @@ void test_cpu_solver_golden() {
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------
+// The solve schedule (schedule.hpp). Layouts and plans only: no field is allocated.
+// ------------------------------------------------------------------------------------------------------------------
+RankSchedule sched(i64 N, int K, const SolverOptions& o, int rank = 0, int world = 1, double free_bytes = 1e13) {
+  Problem p;
+  p.N = N;
+  p.K = K;
+  return make_rank_schedule(p, o, rank, world, free_bytes);
+}
+
+// the units of a fresh solve, started as GpuSolver::phase_init starts it
+std::vector<UnitPlan> fresh_units(const RankSchedule& s) {
+  const bool analytic = (s.mode == Mode::kFusedSingle || s.mode == Mode::kDeepTb) && s.analytic_ok();
+  return plan_units(s, analytic ? 1 : s.opt.init2 && s.prob.K >= 2 ? 2 : 1, analytic);
+}
+
+using Steps = std::vector<std::pair<int, int>>;  // (n, steps) per unit
+Steps steps_of(const std::vector<UnitPlan>& u) {
+  Steps v;
+  for (const UnitPlan& x : u) v.push_back({x.n, x.steps});
+  return v;
+}
+
+void test_unit_lists() {
+  SolverOptions o;
+  std::vector<UnitPlan> u = fresh_units(sched(64, 20, o));
+  CHECK((steps_of(u) == Steps{{1, 4}, {5, 5}, {10, 5}, {15, 5}}));
+  CHECK(u[0].analytic && !u[1].analytic);
+  o.tiling_tb.p2 = false;
+  u = fresh_units(sched(64, 20, o));
+  CHECK((steps_of(u) == Steps{{1, 3}, {4, 4}, {8, 4}, {12, 4}, {16, 4}}));
+  CHECK(u[0].analytic);
+  o = SolverOptions{};
+  o.check_every = 1;  // u¹ carries a check: no analytic start
+  CHECK(!sched(64, 20, o).analytic_ok());
+  u = fresh_units(sched(64, 20, o));
+  CHECK(u[0].n == 2 && !u[0].analytic);
+  o = SolverOptions{};
+  o.tb = false;  // pairs wherever the intermediate step carries no check
+  u = fresh_units(sched(64, 20, o));
+  CHECK((steps_of(u) == Steps{{2, 2}, {4, 2}, {6, 2}, {8, 2}, {10, 2}, {12, 2}, {14, 2}, {16, 2}, {18, 2}}));
+  o.check_every = 3;  // checks at 3, 6, ..., 18, 20
+  u = fresh_units(sched(64, 20, o));
+  CHECK((steps_of(u) == Steps{{2, 1}, {3, 2}, {5, 1}, {6, 2}, {8, 1}, {9, 2}, {11, 1}, {12, 2}, {14, 1}, {15, 2},
+                              {17, 1}, {18, 2}}));
+  o = SolverOptions{};
+  o.temporal = 1;
+  const RankSchedule s1 = sched(64, 20, o);
+  CHECK(s1.mode == Mode::kSingleStep && s1.nbuf == 2);
+  u = plan_units(s1, 1, false);
+  CHECK(u.size() == 19);
+  for (const UnitPlan& x : u) CHECK(x.steps == 1);
+  // every unit list covers start_n..K exactly once
+  std::vector<SolverOptions> opts(6);
+  opts[1].tiling_tb.p2 = false;
+  opts[2].tb = false;
+  opts[3].temporal = 1;
+  opts[4].check_every = 1;
+  opts[5].check_every = 3;
+  for (const SolverOptions& q : opts)
+    for (int K = 3; K <= 25; ++K)
+      for (int world : {1, 2}) {
+        const RankSchedule s = sched(64, K, q, 0, world);
+        u = fresh_units(s);
+        CHECK(!u.empty());
+        int n = u.empty() ? 0 : u[0].n;
+        CHECK(n == 1 || n == 2);
+        for (const UnitPlan& x : u) {
+          CHECK(x.n == n && x.steps >= 1 && x.steps <= s.opt.temporal);
+          n += x.steps;
+        }
+        CHECK(n == K);
+      }
+}
+
+void test_mode_table() {
+  SolverOptions o;
+  for (int world : {2, 4, 8}) {
+    const RankSchedule s = sched(512, 20, o, 1, world);
+    CHECK(s.mode == Mode::kDeepTb && !s.block_tb && s.mode_name() == "deep-tb" && s.opt.temporal == 5 && s.nbuf == 4);
+    CHECK(s.lay.xg == 5 && !s.push);
+    SolverOptions p = o;
+    p.push = true;
+    const RankSchedule t = sched(512, 20, p, 1, world);
+    CHECK(t.mode == Mode::kDeepTb && t.push && t.opt.temporal == 4 && t.lay.xg == 4);
+  }
+  // slab ranks: deep-tb exactly when the smallest rank owns max(tb_min_planes, 2·temporal) = 16 planes
+  for (i64 N = 24; N <= 40; ++N) {
+    Problem p;
+    p.N = N;
+    const i64 mn = imin(rank_box(p, Dims{2, 1, 1}, 0).nx(), rank_box(p, Dims{2, 1, 1}, 1).nx());
+    CHECK((sched(N, 20, o, 0, 2).mode == Mode::kDeepTb) == (mn >= 16));
+  }
+  CHECK(sched(64, 20, o, 0, 8).mode != Mode::kDeepTb);  // 7-8 planes per rank
+  SolverOptions b = o;
+  for (const char* dec : {"2x2x2", "3x3x3"}) {
+    b.decomp = dec;
+    const int world = dec[0] == '2' ? 8 : 27;
+    const RankSchedule s = sched(40, 20, b, 0, world);  // extents 20-21 / 13-14
+    CHECK(s.mode == Mode::kDeepTb && s.block_tb && s.mode_name() == "deep-tb-block" && s.opt.temporal == 5);
+    CHECK(!s.opt.fused_pack && s.lay.xg == 5 && s.lay.yg == 5 && s.lay.zg == 5 && s.send_total >= s.deep_max);
+  }
+  // Smallest block extent 9 (N = 17) or 8 (N = 16): block_fits asks for 2·5 nodes, so the ranks fall to single steps
+  // and temporal is lowered to 4 all the same. ADVICE.md (round 6, low) calls this a silent regression of the S = 4
+  // block passes; the fix (keep deep-tb at temporal 4) changes the next line to Mode::kDeepTb.
+  b.decomp = "2x2x2";
+  for (i64 N : {16, 17}) {
+    const RankSchedule s = sched(N, 20, b, 0, 8);
+    CHECK(s.mode == Mode::kSingleStep);
+    CHECK(s.opt.temporal == 4 && !s.block_tb && s.nbuf == 2);
+  }
+  // memory plan at 2049³: four buffers + 2 GB of headroom must fit, else the two-buffer single-step scheme
+  const double four = 4.0 * static_cast<double>(sched(2049, 20, o).lay.bytes()) + 2.0e9;
+  const RankSchedule lo = sched(2049, 20, o, 0, 1, four - 1e6), hi = sched(2049, 20, o, 0, 1, four + 1e6);
+  CHECK(lo.mode == Mode::kSingleStep && lo.nbuf == 2 && lo.mode_name() == "single-step");
+  CHECK(hi.mode == Mode::kFusedSingle && hi.nbuf == 4);
+  CHECK(throws([&] { sched(2049, 20, o, 0, 1, 1e9); }));
+  // every rank of a world gets the same mode and pass depth
+  const std::vector<std::pair<std::string, int>> worlds = {{"slab", 3}, {"slab", 8}, {"2x2x2", 8}, {"2x2x1", 4}, {"3x3x3", 27}};
+  for (const auto& [dec, world] : worlds)
+    for (i64 N : {17, 40, 100, 130}) {
+      SolverOptions q;
+      q.decomp = dec;
+      const RankSchedule r0 = sched(N, 20, q, 0, world);
+      for (int r = 1; r < world; ++r) {
+        const RankSchedule s = sched(N, 20, q, r, world);
+        CHECK(s.mode == r0.mode && s.opt.temporal == r0.opt.temporal && s.block_tb == r0.block_tb && s.nbuf == r0.nbuf);
+      }
+    }
+}
+
+bool boxes_meet(const LBox& a, const LBox& b) {
+  return imax(a.x0, b.x0) < imin(a.x1, b.x1) && imax(a.y0, b.y0) < imin(a.y1, b.y1) && imax(a.z0, b.z0) < imin(a.z1, b.z1);
+}
+
+// Every deep-tb world of the matrix: both ends of every message agree, message sizes are the region sizes, and the
+// overlapped units' shell boxes and interior tile the compute box on boxes the pair-tiled pass accepts.
+void test_deep_tb_worlds() {
+  const std::vector<std::pair<std::string, int>> worlds = {{"slab", 2}, {"slab", 3}, {"slab", 4}, {"slab", 5}, {"slab", 6},
+                                                           {"slab", 7}, {"slab", 8}, {"2x2x2", 8}, {"2x2x1", 4},
+                                                           {"1x2x2", 4}, {"3x3x3", 27}};
+  for (const auto& [dec, world] : worlds)
+    for (int temporal = 2; temporal <= 5; ++temporal)
+      for (int variant = 0; variant < 4; ++variant) {
+        SolverOptions o;
+        o.decomp = dec;
+        o.temporal = temporal;
+        o.overlap = (variant & 1) != 0;
+        o.ghost_store = (variant & 2) != 0;
+        // (slab worlds 7 and 8 own 12-14 planes per rank at N = 100: below the default 16 no N of the set would do)
+        o.tb_min_planes = 8;
+        // (K = 21: 2-step passes after a 2-step analytic start cannot cover the 19 steps of K = 20 — plan_units
+        // refuses that schedule, as build_units always did)
+        const int K = 21;
+        i64 N = 0;
+        for (i64 n : {40, 64, 100})
+          if (N == 0 && sched(n, K, o, 0, world).mode == Mode::kDeepTb) N = n;
+        CHECK(N != 0);
+        if (N == 0) continue;
+        std::vector<RankSchedule> rs;
+        std::vector<std::vector<UnitPlan>> us;
+        for (int r = 0; r < world; ++r) {
+          rs.push_back(sched(N, K, o, r, world));
+          us.push_back(fresh_units(rs.back()));
+          CHECK(rs.back().opt.temporal == temporal && us.back().size() == us[0].size());
+        }
+        for (int r = 0; r < world; ++r) {
+          const RankSchedule& s = rs[static_cast<size_t>(r)];
+          CHECK(s.side_stream() == o.overlap && s.late_exchange() == !o.overlap && s.overlapped() == o.overlap);
+          for (size_t i = 0; i < us[static_cast<size_t>(r)].size(); ++i) {
+            const UnitPlan& u = us[static_cast<size_t>(r)][i];
+            CHECK(u.exchange == (i + 1 < us[0].size()));
+            if (!u.exchange || !o.overlap) {
+              CHECK(u.shells.empty() && u.interior.count() == s.full.count() && u.interior.x0 == s.full.x0);
+            } else {
+              // shells + interior tile the compute box: inside it, pairwise disjoint, volumes add up
+              std::vector<LBox> all = u.shells;
+              if (!u.interior.empty()) all.push_back(u.interior);
+              i64 vol = 0;
+              for (size_t a = 0; a < all.size(); ++a) {
+                const LBox& b = all[a];
+                vol += b.count();
+                CHECK(!b.empty() && b.x0 >= s.full.x0 && b.x1 <= s.full.x1 && b.y0 >= s.full.y0 && b.y1 <= s.full.y1 &&
+                      b.z0 >= s.full.z0 && b.z1 <= s.full.z1);
+                CHECK(leapfrog_p2_supported(s.lay, b, u.steps));
+                for (size_t c = a + 1; c < all.size(); ++c) CHECK(!boxes_meet(b, all[c]));
+              }
+              CHECK(vol == s.full.count());
+              CHECK(!u.shells.empty() && static_cast<int>(u.shells.size()) < kTbSlots);
+            }
+            if (!u.exchange) {
+              CHECK(u.msgs.empty() && u.ghost_bits == 0);
+              continue;
+            }
+            const int w = us[static_cast<size_t>(r)][i + 1].steps;
+            CHECK(u.depth == w);
+            CHECK(s.block_tb || !o.ghost_store ? u.ghost_bits == 0 : u.ghost_bits == (s.nb[0][0] ? 1 : 0) + (s.nb[0][1] ? 2 : 0));
+            const DeepPlan dp = s.block_tb ? make_deep_plan(s.lay, s.dims, r, w) : DeepPlan{};
+            CHECK(!u.msgs.empty());
+            for (const MsgPlan& m : u.msgs) {
+              const UnitPlan& v = us[static_cast<size_t>(m.peer)][i];
+              int matches = 0;
+              for (const MsgPlan& h : v.msgs)
+                if (h.peer == r && h.tag == m.tag) {
+                  ++matches;
+                  CHECK(h.count == m.count && h.field == m.field);
+                }
+              CHECK(matches == 1);
+              if (s.block_tb) {
+                i64 want = -1;
+                for (const DeepPeer& q : dp.peers)
+                  if (q.peer == m.peer) want = q.count;
+                CHECK(m.count == want && m.field == MsgField::kStaging && m.send_off + m.count <= s.send_total &&
+                      m.recv_off + m.count <= s.deep_max);
+              } else {
+                // slab: S' planes of u^{n+S}, S' − 1 − g of u^{n+S−1}; both ends store the same ghost plane or neither
+                const int side = m.peer < r ? 0 : 1, g = (u.ghost_bits >> side) & 1;
+                CHECK(((v.ghost_bits >> (1 - side)) & 1) == g);
+                CHECK(m.count == (m.tag == 0 ? w : w - 1 - g) * s.lay.plane);
+                CHECK(m.field == (m.tag == 0 ? MsgField::kOut2 : MsgField::kOut1));
+                CHECK(m.send_off >= s.lay.plane_off(0) && m.send_off + m.count <= s.lay.plane_off(s.lay.nx));
+                CHECK(m.recv_off >= 0 && m.recv_off + m.count <= s.lay.total &&
+                      (m.recv_off + m.count <= s.lay.plane_off(0) || m.recv_off >= s.lay.plane_off(s.lay.nx)));
+              }
+            }
+          }
+        }
+      }
+}
+
+void test_traffic() {
+  // slab S = 5, K = 20, N = 512, world 8, an inner rank: three exchanges of 5 planes of u^{n+S} and 4 (ghost_store: 3)
+  // of u^{n+S−1} per face (docs/ARCHITECTURE.md: 60.5 → 53.8 MB is the same 27 : 24)
+  for (bool gs : {true, false}) {
+    SolverOptions o;
+    o.ghost_store = gs;
+    const RankSchedule s = sched(512, 20, o, 3, 8);
+    const std::vector<UnitPlan> u = fresh_units(s);
+    CHECK((steps_of(u) == Steps{{1, 4}, {5, 5}, {10, 5}, {15, 5}}));
+    const Traffic t = traffic(s, u, false);
+    CHECK(t.halo_bytes == 2.0 * (gs ? 24.0 : 27.0) * static_cast<double>(s.lay.plane) * 8.0);
+  }
+  // one rank: an analytic-start pass writes two levels, a fused pass moves four, a single step three, the init two
+  for (bool tb : {true, false}) {
+    SolverOptions o;
+    o.tb = tb;
+    o.check_every = 3;
+    const RankSchedule s = sched(64, 20, o);
+    const std::vector<UnitPlan> u = fresh_units(s);
+    const double nb = 63.0 * 63.0 * 63.0 * 8.0;
+    double want = u[0].analytic ? 0.0 : 2.0 * nb;
+    for (const UnitPlan& x : u) want += nb * (x.analytic ? 2.0 : x.steps >= 2 ? 4.0 : 3.0);
+    const Traffic t = traffic(s, u, !u[0].analytic);
+    CHECK(u[0].analytic == tb);
+    CHECK(t.field_bytes == want && t.halo_bytes == 0.0);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -233,6 +494,10 @@ int main() {
   test_problem();
   test_pack_unpack();
   test_cpu_solver_golden();
+  test_unit_lists();
+  test_mode_table();
+  test_deep_tb_worlds();
+  test_traffic();
   std::printf("test_core: %d checks, %d failed\n", g_checks, g_fail);
   return g_fail == 0 ? 0 : 1;
 }

@@ -10,7 +10,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["csrc/tests/test_core.cpp", "csrc/src/cpu_kernels.cpp", "csrc/src/cpu_solver.cpp"]
+SOURCES = ["csrc/tests/test_core.cpp", "csrc/src/cpu_kernels.cpp", "csrc/src/cpu_solver.cpp", "csrc/src/schedule.cpp"]
 
 
 @pytest.fixture(scope="module")

@@ -62,6 +62,7 @@ LIB_SOURCES = [
     ("src/runtime_launch.cpp", "hip"),
     ("src/runtime_io.cpp", "hip"),
     ("src/runtime_autotune.cpp", "hip"),
+    ("src/schedule.cpp", "cpu"),
     ("src/cpu_kernels.cpp", "cpu"),
     ("src/cpu_solver.cpp", "cpu"),
     ("src/cpu_dist.cpp", "cpu"),

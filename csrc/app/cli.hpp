@@ -16,6 +16,8 @@ namespace wave3d::cli {
 struct Args {
   Problem prob;
   bool have_L = false;
+  bool have_box = false;  // --box LX,LY,LZ: a rectangular box (prob.L, Ly, Lz); excludes the positional L
+  double box[3] = {0.0, 0.0, 0.0};
   std::string decomp = "slab";
   int check_every = 2;
   bool cpu = false;
@@ -81,6 +83,10 @@ void print_errors(const std::vector<int>& steps, const std::vector<double>& mx, 
 std::string jstr(const std::string& v);
 std::string json_escape(const std::string& v);
 std::string jnum(double v);
+// a rectangular box's three edges for the banner (" box=LX,LY,LZ") and the JSON summaries (", \"box\": [LX, LY, LZ]");
+// empty for a cube, whose lines stay what they were
+std::string box_banner(const Problem& p);
+std::string box_json(const Problem& p);
 std::string steps_json(const std::vector<int>& st, const std::vector<double>& mx, const std::vector<double>& rms);
 // solver options from the command line
 SolverOptions options_from(const Args& a, bool fake);

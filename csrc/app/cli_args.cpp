@@ -41,6 +41,8 @@ constexpr Personality kPersonalities[] = {
                "  N        intervals per axis ((N+1)^3 nodes)      tau   time step\n"
                "  K        number of steps                          L     cube edge (default 1)\n"
                "options:\n"
+               "  --box LX,LY,LZ     rectangular box [0,LX]x[0,LY]x[0,LZ], the same N per axis (instead of the positional\n"
+               "                     L; every program personality)\n"
                "  --np P             spawn P ranks on this node (one GPU each; with --cpu: P CPU processes, the\n"
                "                     reference's MPI / MPI+OpenMP programs, halos through shared memory)\n"
                "  --decomp D         slab | block | PxQxR (default slab)\n"
@@ -186,6 +188,30 @@ Args parse(int argc, char** argv) {
     else if (s == "--dump") a.dump = next();
     else if (s == "--checkpoint") a.checkpoint = next();
     else if (s == "--resume") a.resume = next();
+    else if (s == "--box") {
+      const std::string v = next();  // LX,LY,LZ
+      double e[3] = {0.0, 0.0, 0.0};
+      size_t at = 0;
+      int n = 0;
+      try {
+        for (; n < 3; ++n) {
+          const size_t c = v.find(',', at);
+          if ((c == std::string::npos) != (n == 2)) break;
+          size_t used = 0;
+          const std::string part = v.substr(at, c == std::string::npos ? std::string::npos : c - at);
+          e[n] = std::stod(part, &used);
+          if (used != part.size()) break;
+          at = c + 1;
+        }
+      } catch (const std::exception&) {
+        n = -1;
+      }
+      if (n != 3 || !(e[0] > 0.0) || !(e[1] > 0.0) || !(e[2] > 0.0)) usage("--box expects three positive edges LX,LY,LZ");
+      a.box[0] = e[0];
+      a.box[1] = e[1];
+      a.box[2] = e[2];
+      a.have_box = true;
+    }
     else if (s == "--force") a.force = true;
     else if (s == "--quiet") a.quiet = true;
     else if (s == "-h" || s == "--help") usage();
@@ -201,9 +227,15 @@ Args parse(int argc, char** argv) {
     if (pers && pers->pos4_threads) {
       a.threads = std::stoi(pos[3]);
     } else {
+      if (a.have_box) usage("--box and the positional L exclude each other");
       a.prob.L = std::stod(pos[3]);
       a.have_L = true;
     }
+  }
+  if (a.have_box) {
+    a.prob.L = a.box[0];
+    a.prob.Ly = a.box[1];
+    a.prob.Lz = a.box[2];
   }
   if (a.repeat < 1) a.repeat = 1;
   return a;
@@ -229,6 +261,16 @@ std::string jnum(double v) {
   char b[64];
   std::snprintf(b, sizeof b, "%.10g", v);
   return b;
+}
+std::string box_banner(const Problem& p) {
+  if (!p.is_box()) return "";
+  char b[128];
+  std::snprintf(b, sizeof b, " box=%g,%g,%g", p.L, p.edge_y(), p.edge_z());
+  return b;
+}
+std::string box_json(const Problem& p) {
+  if (!p.is_box()) return "";
+  return ", \"box\": [" + jexact(p.L) + ", " + jexact(p.edge_y()) + ", " + jexact(p.edge_z()) + "]";
 }
 std::string steps_json(const std::vector<int>& st, const std::vector<double>& mx, const std::vector<double>& rms) {
   std::string o = "[";

@@ -168,9 +168,9 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
   }
   const Dims d = g.rank(0).dims();
   if (!a.quiet) {
-    std::printf("wave3d: N=%lld tau=%g K=%d L=%g group of %d ranks (%s) decomp=%dx%dx%d device=%s\n",
-                static_cast<long long>(a.prob.N), a.prob.tau, a.prob.K, a.prob.L, a.group, a.group_transport.c_str(),
-                d.px, d.py, d.pz, prop.gcnArchName);
+    std::printf("wave3d: N=%lld tau=%g K=%d L=%g%s group of %d ranks (%s) decomp=%dx%dx%d device=%s\n",
+                static_cast<long long>(a.prob.N), a.prob.tau, a.prob.K, a.prob.L, box_banner(a.prob).c_str(), a.group,
+                a.group_transport.c_str(), d.px, d.py, d.pz, prop.gcnArchName);
     print_errors(r.steps, r.max_err, r.rms_err, a.prob.tau);
   }
   std::printf("Total time: %.6f s (group solve on one GPU; best of %d, mean %.6f s); schedule %s, graph %s\n", best,
@@ -185,7 +185,7 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
   if (!a.json.empty()) {
     std::vector<int> cc = g.comm_counts();
     std::ofstream j(a.json);
-    j << "{\"backend\": \"hip\", \"group\": " << a.group << ", \"transport\": " << jstr(a.group_transport)
+    j << "{\"backend\": \"hip\", \"group\": " << a.group << box_json(a.prob) << ", \"transport\": " << jstr(a.group_transport)
       << ", \"graph\": " << (g.graph_enabled() ? "true" : "false") << ", \"schedule\": " << jstr(g.rank(0).mode())
       << ", \"temporal\": " << g.rank(0).options().temporal << ", \"rccl_comms\": " << cc.size() << ", \"solve_s\": " << jnum(best) << ", \"steps\": [";
     for (size_t i = 0; i < r.steps.size(); ++i)
@@ -367,9 +367,9 @@ int run_gpu(const Args& a) {
   (void)hipRuntimeGetVersion(&hipv);
   if (rank == 0 || fake) {
     if (!a.quiet) {
-      std::printf("wave3d: N=%lld tau=%g K=%d L=%g ranks=%d decomp=%dx%dx%d device=%s courant=%.3f\n",
-                  static_cast<long long>(a.prob.N), a.prob.tau, a.prob.K, a.prob.L, world, d.px, d.py, d.pz,
-                  prop.gcnArchName, a.prob.courant());
+      std::printf("wave3d: N=%lld tau=%g K=%d L=%g%s ranks=%d decomp=%dx%dx%d device=%s courant=%.3f\n",
+                  static_cast<long long>(a.prob.N), a.prob.tau, a.prob.K, a.prob.L, box_banner(a.prob).c_str(), world,
+                  d.px, d.py, d.pz, prop.gcnArchName, a.prob.courant());
       print_errors(r.steps, r.max_err, r.rms_err, a.prob.tau);
     }
     const double gcell = a.prob.cell_updates() / best / 1e9;
@@ -397,7 +397,7 @@ int run_gpu(const Args& a) {
     if (!a.json.empty()) {
       std::ofstream j(a.json);
       j << "{\"backend\": \"hip\", \"N\": " << a.prob.N << ", \"tau\": " << jnum(a.prob.tau) << ", \"K\": " << a.prob.K
-        << ", \"L\": " << jnum(a.prob.L) << ", \"ranks\": " << world << ", \"dims\": [" << d.px << ", " << d.py
+        << ", \"L\": " << jnum(a.prob.L) << box_json(a.prob) << ", \"ranks\": " << world << ", \"dims\": [" << d.px << ", " << d.py
         << ", " << d.pz << "], \"solve_s\": " << jnum(best) << ", \"mean_s\": " << jnum(mean)
         << ", \"first_s\": " << jnum(first) << ", \"process_s\": " << jnum(t_proc) << ", \"rccl_init_s\": "
         << jnum(t_comm) << ", \"rccl_nranks\": " << rccl_nranks << ", \"rccl_version\": " << rccl_version()
@@ -459,11 +459,18 @@ int main(int argc, char** argv) {
     Args a = parse(argc, argv);
     a.prob.validate();
     if (!a.prob.cfl_ok()) {
-      std::fprintf(stderr,
-                   "wave3d: CFL violated: courant = tau*sqrt(3)/h = %.4f > 1 (tau_max = %.3e for N=%lld, L=%g); the "
-                   "leapfrog scheme is unstable.%s\n",
-                   a.prob.courant(), a.prob.tau_max(), static_cast<long long>(a.prob.N), a.prob.L,
-                   a.force ? " Continuing (--force)." : " Use a smaller tau, or --force.");
+      if (a.prob.is_box())
+        std::fprintf(stderr,
+                     "wave3d: CFL violated: courant = tau*sqrt(1/hx^2+1/hy^2+1/hz^2) = %.4f > 1 (tau_max = %.3e for "
+                     "N=%lld, box %g,%g,%g); the leapfrog scheme is unstable.%s\n",
+                     a.prob.courant(), a.prob.tau_max(), static_cast<long long>(a.prob.N), a.prob.L, a.prob.edge_y(),
+                     a.prob.edge_z(), a.force ? " Continuing (--force)." : " Use a smaller tau, or --force.");
+      else
+        std::fprintf(stderr,
+                     "wave3d: CFL violated: courant = tau*sqrt(3)/h = %.4f > 1 (tau_max = %.3e for N=%lld, L=%g); the "
+                     "leapfrog scheme is unstable.%s\n",
+                     a.prob.courant(), a.prob.tau_max(), static_cast<long long>(a.prob.N), a.prob.L,
+                     a.force ? " Continuing (--force)." : " Use a smaller tau, or --force.");
       if (!a.force) return 2;
     }
     // multi-process CPU path: the shared segment is mapped before the fork so every rank inherits it (--np), or, for

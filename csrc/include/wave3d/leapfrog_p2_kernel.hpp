@@ -306,6 +306,7 @@ struct P2Params {
   int check_mask;
   double tau2, half_tau2;
   double ct[5];
+  double ry, rz;  // rectangular box (BOX instantiations): h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box)
 #ifdef W3D_EXPERIMENT_WGTIME
   unsigned long long* wgtime;  // (perf study) 4 wall-clock stamps per workgroup, pinned host memory
 #endif
@@ -394,7 +395,10 @@ __device__ __forceinline__ int p2_desc(int tid) {
 // p2_attribution.md): deferred stores, two-plane-ahead prefetch, staggered waves, conditional queue writes, the late
 // u^n load point, row-major halo lanes, split stores in the analytic start, stores from every wave, a separate
 // interior-tile body, Dirichlet selects after every stage, the ring waves loading u^{n−1}, a φ plane in LDS.
-template <int S, int CM, bool INIT, bool CH>
+// BOX: a rectangular box — every Laplacian is d2sum_box with the ratios p.ry, p.rz (wave-uniform kernel arguments:
+// scalar operands of two v_fma_f64 that replace two v_add_f64, no vector register more). Cube problems launch the
+// BOX = false instantiations, whose code is what it was before the flag existed.
+template <int S, int CM, bool INIT, bool CH, bool BOX = false>
 __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
   using G = Geo<S>;
   constexpr int E = G::E, R0 = G::R0, R1 = G::R1;
@@ -595,8 +599,9 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
       const double sxc = sxw[xi], sy = syw[yb], sz = szw[zb];
       const double cy = sxc * sy;
       const double c = cy * sz;
-      const double lap = d2sum(c, (sxw[xi - 1] * sy) * sz, (sxw[xi + 1] * sy) * sz, (sxc * syw[yb - 1]) * sz,
-                               (sxc * syw[yb + 1]) * sz, cy * szw[zb - 1], cy * szw[zb + 1]);
+      const double lap =
+          d2sum_t<BOX>(c, (sxw[xi - 1] * sy) * sz, (sxw[xi + 1] * sy) * sz, (sxc * syw[yb - 1]) * sz,
+                       (sxc * syw[yb + 1]) * sz, cy * szw[zb - 1], cy * szw[zb + 1], p.ry, p.rz);
       return (real_yz && inside(p.gx0 + x)) ? first_step(c, lap, p.half_tau2) : 0.0;
     };
     auto u1_pair = [&](int x) __attribute__((always_inline)) {
@@ -666,8 +671,8 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
           zm = rd1(bk, ok_(pl, 0, -1) + 8);
           zq = rd1(bk, ok_(pl, 0, 1));
         }
-        const double lapl = d2sum(c.x, xm.x, xq.x, ym.x, yp.x, zm, c.y);
-        const double laph = d2sum(c.y, xm.y, xq.y, ym.y, yp.y, c.x, zq);
+        const double lapl = d2sum_t<BOX>(c.x, xm.x, xq.x, ym.x, yp.x, zm, c.y, p.ry, p.rz);
+        const double laph = d2sum_t<BOX>(c.y, xm.y, xq.y, ym.y, yp.y, c.x, zq, p.ry, p.rz);
         const D2 o = k == 1 ? Lm[kLate ? 0 : (D & 1)] : L[k > 1 ? k - 2 : 0][s0];
         v = D2m(leapfrog(c.x, o.x, lapl, lam_lo), leapfrog(c.y, o.y, laph, lam_hi));
         if constexpr (!BK) {
@@ -754,8 +759,8 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
         const double ry_m = sx2 * syw[a + 1], ry_p = sx2 * syw[a + 3], cy2 = sx2 * fy;
         const D2 ym = D2m(ry_m * fzl, ry_m * fzh), yp = D2m(ry_p * fzl, ry_p * fzh);
         const double zm = cy2 * szw[2 * b + 3], zq = cy2 * szw[2 * b + 6];
-        const double lapl = d2sum(c.x, f1.x, f3.x, ym.x, yp.x, zm, c.y);
-        const double laph = d2sum(c.y, f1.y, f3.y, ym.y, yp.y, c.x, zq);
+        const double lapl = d2sum_t<BOX>(c.x, f1.x, f3.x, ym.x, yp.x, zm, c.y, p.ry, p.rz);
+        const double laph = d2sum_t<BOX>(c.y, f1.y, f3.y, ym.y, yp.y, c.x, zq, p.ry, p.rz);
         u = D2m(first_step(c.x, lapl, p.half_tau2), first_step(c.y, laph, p.half_tau2));
         u.x = rl ? u.x : 0.0;
         u.y = rh ? u.y : 0.0;

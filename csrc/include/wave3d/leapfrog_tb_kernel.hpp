@@ -84,6 +84,7 @@ struct TbParams {
   // fused z-face pack (TbPack; nullptr: none): nodes with z outside [pkza, pkzb) lie in a z send band of width w
   const TbPack* pk;
   int pkza, pkzb;
+  double ry, rz;       // rectangular box (BOX instantiations): h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box)
 };
 
 // Push transport memory protocol. The staging is fine-grained device memory (hipDeviceMallocFinegrained; W3D_PUSH_STAGING=
@@ -203,7 +204,9 @@ constexpr int tb_nx_table(int nx_box) {
 // (k_init_first's formulas and operation order) instead of loaded: the pass reads nothing from HBM.
 // CH: x-chunked launch (small boxes). Without it the block's x range is the kernel argument itself, which the compiler
 // re-reads instead of keeping live (measured: a computed range costs the S = 4 kernel 5 % in extra spills).
-template <int S, int T, int NT, int CM, bool INIT, bool CH, bool PUSH>
+// BOX: a rectangular box — every Laplacian is d2sum_box with the wave-uniform ratios p.ry, p.rz (two v_add_f64 become
+// two v_fma_f64 with a scalar operand). Cube problems launch the BOX = false instantiations, unchanged by the flag.
+template <int S, int T, int NT, int CM, bool INIT, bool CH, bool PUSH, bool BOX = false>
 __global__ __launch_bounds__(NT) void k_leapfrog_tb(const TbParams p) {
   using G = TbGeom<S, T, NT, tb_row_pad<INIT, S>>;
   constexpr int Q = G::Q, QR = G::QR, H1 = G::H1, W0 = G::W0, RS = G::RS, PLP = G::PLP;
@@ -387,8 +390,9 @@ __global__ __launch_bounds__(NT) void k_leapfrog_tb(const TbParams p) {
       const double sxc = sxw[xi], sy = syw[ya], sz = szw[zb];
       const double cy = sxc * sy;
       const double c = cy * sz;
-      const double lap = d2sum(c, (sxw[xi - 1] * sy) * sz, (sxw[xi + 1] * sy) * sz, (sxc * syw[ya - 1]) * sz,
-                              (sxc * syw[ya + 1]) * sz, cy * szw[zb - 1], cy * szw[zb + 1]);
+      const double lap =
+          d2sum_t<BOX>(c, (sxw[xi - 1] * sy) * sz, (sxw[xi + 1] * sy) * sz, (sxc * syw[ya - 1]) * sz,
+                       (sxc * syw[ya + 1]) * sz, cy * szw[zb - 1], cy * szw[zb + 1], p.ry, p.rz);
       return (real_yz && inside(p.gx0 + x)) ? first_step(c, lap, p.half_tau2) : 0.0;
     };
 
@@ -537,8 +541,8 @@ __global__ __launch_bounds__(NT) void k_leapfrog_tb(const TbParams p) {
         const double f3 = (sx3 * fyq(q)) * fzq(q);   // φ(i+3)
         p3[li] = f3;
         const double c = p2[li];                     // φ(i+2)
-        const double lap =
-            d2sum(c, f1, f3, lds_rd(p2 + li - RS), lds_rd(p2 + li + RS), lds_rd(p2 + li - 1), lds_rd(p2 + li + 1));
+        const double lap = d2sum_t<BOX>(c, f1, f3, lds_rd(p2 + li - RS), lds_rd(p2 + li + RS), lds_rd(p2 + li - 1),
+                                        lds_rd(p2 + li + 1), p.ry, p.rz);
         L[0][q][(F + 2) & 3] = ((gof[q] & kLd) && xin) ? first_step(c, lap, p.half_tau2) : 0.0;
         Lm[q][(F + 1) & 1] = f1;
       }
@@ -616,12 +620,12 @@ __global__ __launch_bounds__(NT) void k_leapfrog_tb(const TbParams p) {
         const double c = L[k - 1][q][s0];
         double lap;
         if constexpr (k == 1) {
-          lap = d2sum(c, L[k - 1][q][sm], L[k - 1][q][sp], lds_rd(nb + li - RS), lds_rd(nb + li + RS),
-                      lds_rd(nb + li - 1), lds_rd(nb + li + 1));
+          lap = d2sum_t<BOX>(c, L[k - 1][q][sm], L[k - 1][q][sp], lds_rd(nb + li - RS), lds_rd(nb + li + RS),
+                             lds_rd(nb + li - 1), lds_rd(nb + li + 1), p.ry, p.rz);
         } else {
           const int lc = tid + q * NT;  // (compact index: the position itself)
-          lap = d2sum(c, L[k - 1][q][sm], L[k - 1][q][sp], lds_rd(nb + lc - H1), lds_rd(nb + lc + H1),
-                      lds_rd(nb + lc - 1), lds_rd(nb + lc + 1));
+          lap = d2sum_t<BOX>(c, L[k - 1][q][sm], L[k - 1][q][sp], lds_rd(nb + lc - H1), lds_rd(nb + lc + H1),
+                             lds_rd(nb + lc - 1), lds_rd(nb + lc + 1), p.ry, p.rz);
         }
         double o;
         if constexpr (k == 1)
@@ -930,12 +934,12 @@ constexpr size_t max_dyn_lds() {
 // allow the dynamic LDS size once per instantiation (outside any stream capture: see leapfrog_tb_prepare): the CU's
 // 160 KiB minus the kernel's static LDS (the reduction arrays as the compiler laid them out, alignment included);
 // returns that limit
-template <int S, int NT, int CM, bool INIT, bool CH, bool PUSH>
+template <int S, int NT, int CM, bool INIT, bool CH, bool PUSH, bool BOX = false>
 size_t prepare_cfg() {
   static_assert(tb_lds_bytes<S, kTile, NT, INIT, (CM != 0 && !INIT)>() <= max_dyn_lds<NT>(),
                 "leapfrog_tb tile does not fit in LDS");
   static const size_t limit = [] {
-    const void* fn = reinterpret_cast<const void*>(k_leapfrog_tb<S, kTile, NT, CM, INIT, CH, PUSH>);
+    const void* fn = reinterpret_cast<const void*>(k_leapfrog_tb<S, kTile, NT, CM, INIT, CH, PUSH, BOX>);
     hipFuncAttributes fa{};
     hipError_t e = hipFuncGetAttributes(&fa, fn);
     if (e != hipSuccess) fail(std::string("leapfrog_tb attributes: ") + hipGetErrorString(e));
@@ -947,20 +951,20 @@ size_t prepare_cfg() {
   return limit;
 }
 
-template <int S, int NT, int CM, bool INIT, bool PUSH>
+template <int S, int NT, int CM, bool INIT, bool PUSH, bool BOX = false>
 void launch_cfg(const TbParams& p, int nblocks, hipStream_t st) {
   const size_t shmem = tb_lds_bytes<S, kTile, NT, INIT, (CM != 0 && !INIT)>(
                            (p.check_mask || INIT) ? tb_nx_table<S>(p.xlen) : 0) +
                        (PUSH ? 8 * sizeof(unsigned long long) : 0) +  // (the push block: staging pointers)
                        sizeof(TbPack);                                 // (the fused-pack block)
   if (p.nxc > 1) {
-    const size_t lim = prepare_cfg<S, NT, CM, INIT, true, PUSH>();
+    const size_t lim = prepare_cfg<S, NT, CM, INIT, true, PUSH, BOX>();
     W3D_REQUIRE(shmem <= lim, "leapfrog_tb: too many planes for the LDS sin table");
-    hipLaunchKernelGGL((k_leapfrog_tb<S, kTile, NT, CM, INIT, true, PUSH>), dim3(nblocks), dim3(NT), shmem, st, p);
+    hipLaunchKernelGGL((k_leapfrog_tb<S, kTile, NT, CM, INIT, true, PUSH, BOX>), dim3(nblocks), dim3(NT), shmem, st, p);
   } else {
-    const size_t lim = prepare_cfg<S, NT, CM, INIT, false, PUSH>();
+    const size_t lim = prepare_cfg<S, NT, CM, INIT, false, PUSH, BOX>();
     W3D_REQUIRE(shmem <= lim, "leapfrog_tb: too many planes for the LDS sin table");
-    hipLaunchKernelGGL((k_leapfrog_tb<S, kTile, NT, CM, INIT, false, PUSH>), dim3(nblocks), dim3(NT), shmem, st, p);
+    hipLaunchKernelGGL((k_leapfrog_tb<S, kTile, NT, CM, INIT, false, PUSH, BOX>), dim3(nblocks), dim3(NT), shmem, st, p);
   }
 }
 
@@ -972,42 +976,47 @@ constexpr int kEven = 0b1010 & kFull<S>;
 template <int S>
 constexpr int kOdd = 0b0101 & kFull<S>;
 
-template <int S, int NT, bool INIT, bool PUSH>
+template <int S, int NT, bool INIT, bool PUSH, bool BOX = false>
 void launch_nt(const TbParams& p, int nblocks, hipStream_t st) {
   const int m = p.check_mask;
   if (m == 0)
-    launch_cfg<S, NT, 0, INIT, PUSH>(p, nblocks, st);
+    launch_cfg<S, NT, 0, INIT, PUSH, BOX>(p, nblocks, st);
   else if ((m & ~kEven<S>) == 0)
-    launch_cfg<S, NT, kEven<S>, INIT, PUSH>(p, nblocks, st);
+    launch_cfg<S, NT, kEven<S>, INIT, PUSH, BOX>(p, nblocks, st);
   else if ((m & ~kOdd<S>) == 0)
-    launch_cfg<S, NT, kOdd<S>, INIT, PUSH>(p, nblocks, st);
+    launch_cfg<S, NT, kOdd<S>, INIT, PUSH, BOX>(p, nblocks, st);
   else
-    launch_cfg<S, NT, kFull<S>, INIT, PUSH>(p, nblocks, st);
+    launch_cfg<S, NT, kFull<S>, INIT, PUSH, BOX>(p, nblocks, st);
 }
 
 // workgroup size per pass kind: LeapfrogTbTiling::threads, or init_threads for the analytic-start pass
-template <int S, bool PUSH>
+template <int S, bool PUSH, bool BOX = false>
 void launch_s(const TbParams& p, int nblocks, const LeapfrogTbTiling& t, bool init, hipStream_t st) {
   // 768 threads: 12 waves (3 per SIMD, 168 VGPRs each) for the 38² = 1444 stage-1 positions of an S = 4 tile, two sets
   // per thread with 6 % idle slots; 1024: 16 waves (128 VGPRs), 30 % of the second set idle
   if ((init ? t.init_threads : t.threads) == 768)
-    init ? launch_nt<S, 768, true, PUSH>(p, nblocks, st) : launch_nt<S, 768, false, PUSH>(p, nblocks, st);
+    init ? launch_nt<S, 768, true, PUSH, BOX>(p, nblocks, st) : launch_nt<S, 768, false, PUSH, BOX>(p, nblocks, st);
   else
-    init ? launch_nt<S, 1024, true, PUSH>(p, nblocks, st) : launch_nt<S, 1024, false, PUSH>(p, nblocks, st);
+    init ? launch_nt<S, 1024, true, PUSH, BOX>(p, nblocks, st) : launch_nt<S, 1024, false, PUSH, BOX>(p, nblocks, st);
 }
 
-template <int S, int NT, bool INIT, bool CH, bool PUSH>
+template <int S, int NT, bool INIT, bool CH, bool PUSH, bool BOX = false>
 void prepare_ch() {
-  prepare_cfg<S, NT, 0, INIT, CH, PUSH>();
-  prepare_cfg<S, NT, kEven<S>, INIT, CH, PUSH>();
-  prepare_cfg<S, NT, kOdd<S>, INIT, CH, PUSH>();
-  prepare_cfg<S, NT, kFull<S>, INIT, CH, PUSH>();
+  prepare_cfg<S, NT, 0, INIT, CH, PUSH, BOX>();
+  prepare_cfg<S, NT, kEven<S>, INIT, CH, PUSH, BOX>();
+  prepare_cfg<S, NT, kOdd<S>, INIT, CH, PUSH, BOX>();
+  prepare_cfg<S, NT, kFull<S>, INIT, CH, PUSH, BOX>();
 }
-template <int S, int NT, bool INIT, bool PUSH = false>
+template <int S, int NT, bool INIT, bool PUSH = false, bool BOX = false>
 void prepare_nt() {
-  prepare_ch<S, NT, INIT, false, PUSH>();
-  prepare_ch<S, NT, INIT, true, PUSH>();
+  prepare_ch<S, NT, INIT, false, PUSH, BOX>();
+  prepare_ch<S, NT, INIT, true, PUSH, BOX>();
 }
+
+// rectangular-box instantiations (kernels_leapfrog_tb_box.hip; BOX = true, PUSH = false): the same S / workgroup size /
+// check-mask / chunk sets as the cube's
+void launch_box(const TbParams& p, int nblocks, const LeapfrogTbTiling& t, bool init, hipStream_t st);
+void prepare_box();
 
 
 // push transport instantiations (kernels_leapfrog_tb_push.hip): 1024-thread workgroups (analytic start: init_threads)

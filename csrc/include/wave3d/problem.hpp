@@ -6,6 +6,9 @@
 //   * u^0 = φ, u^1 = u^0 + τ²/2 Δ_h u^0, u^{n+1} = 2u^n − u^{n−1} + τ² Δ_h u^n   (report.pdf p.5 §2.2)
 //   * analytic u_a = sin(πx/L) sin(πy/L) sin(πz/L) cos(a_t t), a_t = π√3/L        (report.pdf p.4 §1)
 //   * CLI positional "N tau K [L]"                                   (report.pdf p.15 §4.2.4)
+//   * rectangular box [0,Lx]×[0,Ly]×[0,Lz] with the same N per axis: u_a = Π_d sin(π x_d/L_d)·cos(a_t t),
+//     a_t = π√(1/Lx²+1/Ly²+1/Lz²), h_d = L_d/N (report.pdf p.4 §1). The sine table is the cube's:
+//     sin(π·i·h_d/L_d) = sin(π·i/N) on every axis.
 #pragma once
 
 #include <cmath>
@@ -19,17 +22,37 @@ struct Problem {
   i64 N = 512;        // number of intervals per axis → (N+1)^3 nodes
   double tau = 1e-3;  // time step
   int K = 20;         // number of time steps
-  double L = 1.0;     // cube edge length (Lx = Ly = Lz = L)
+  double L = 1.0;     // edge length in x (Lx); a cube's only edge
+  double Ly = 0.0;    // edge lengths in y and z of a rectangular box; ≤ 0: "= L"
+  double Lz = 0.0;
 
+  double Lx() const { return L; }
+  double edge_y() const { return Ly > 0.0 ? Ly : L; }
+  double edge_z() const { return Lz > 0.0 ? Lz : L; }
+  // A problem whose three edges are equal is a cube: it keeps the cube's expressions below (and the cube's kernels),
+  // so giving Ly = Lz = L changes no bit of a cube's results.
+  bool is_box() const { return edge_y() != L || edge_z() != L; }
   double h() const { return L / static_cast<double>(N); }
+  double hx() const { return h(); }
+  double hy() const { return edge_y() / static_cast<double>(N); }
+  double hz() const { return edge_z() / static_cast<double>(N); }
   i64 nodes() const { return N + 1; }
+  // Σ_d 1/h_d², summed as (x + y) + z (the Python side uses the same order: same bits)
+  double inv_h2_sum() const {
+    const double a = hx(), b = hy(), c = hz();
+    return (1.0 / (a * a) + 1.0 / (b * b)) + 1.0 / (c * c);
+  }
   // a_t = π·sqrt(1/Lx² + 1/Ly² + 1/Lz²)
-  double a_t() const { return M_PI * std::sqrt(3.0 / (L * L)); }
-  // Courant number for the 3D 7-point leapfrog: stable iff τ·sqrt(3)/h ≤ 1.
-  double courant() const { return tau * std::sqrt(3.0) / h(); }
+  double a_t() const {
+    if (!is_box()) return M_PI * std::sqrt(3.0 / (L * L));
+    const double ly = edge_y(), lz = edge_z();
+    return M_PI * std::sqrt((1.0 / (L * L) + 1.0 / (ly * ly)) + 1.0 / (lz * lz));
+  }
+  // Courant number for the 3D 7-point leapfrog: stable iff τ·sqrt(Σ 1/h_d²) ≤ 1 (cube: τ·sqrt(3)/h).
+  double courant() const { return is_box() ? tau * std::sqrt(inv_h2_sum()) : tau * std::sqrt(3.0) / h(); }
   bool cfl_ok() const { return courant() <= 1.0; }
   // Largest stable τ for this grid.
-  double tau_max() const { return h() / std::sqrt(3.0); }
+  double tau_max() const { return is_box() ? 1.0 / std::sqrt(inv_h2_sum()) : h() / std::sqrt(3.0); }
   // Cell updates of one full solve (reference convention for GCell/s: N³·K).
   double cell_updates() const { return static_cast<double>(N) * N * N * K; }
 
@@ -38,6 +61,7 @@ struct Problem {
     W3D_REQUIRE(tau > 0.0 && std::isfinite(tau), "tau must be > 0");
     W3D_REQUIRE(K >= 1, "K must be >= 1");
     W3D_REQUIRE(L > 0.0 && std::isfinite(L), "L must be > 0");
+    W3D_REQUIRE(std::isfinite(Ly) && std::isfinite(Lz), "box edges must be finite");
   }
 };
 
@@ -48,8 +72,13 @@ struct Coeffs {
   double half_tau2;         // τ²/2
   double lam;               // τ²/h²: the update coefficient of d2sum (stencil.hpp)
   double half_lam;          // (τ²/2)/h²
+  // Rectangular box (stencil.hpp::d2sum_box): the y and z differences are weighted by h_x²/h_y², h_x²/h_z² and lam,
+  // half_lam carry 1/h_x². `box` selects that form in every kernel; a cube has box = false, ry = rz = 1.
+  double ry = 1.0, rz = 1.0;
+  bool box = false;
 
-  static Coeffs from(const Problem& p) {
+  // force_box (tests): the box form also for a cube — with ry = rz = 1 it must reproduce the cube form's bits
+  static Coeffs from(const Problem& p, bool force_box = false) {
     Coeffs c;
     const double h = p.h();
     c.ihx2 = 1.0 / (h * h);
@@ -59,6 +88,14 @@ struct Coeffs {
     c.half_tau2 = 0.5 * c.tau2;
     c.lam = c.tau2 * c.ihx2;
     c.half_lam = c.half_tau2 * c.ihx2;
+    if (p.is_box()) {
+      const double hy = p.hy(), hz = p.hz();
+      c.ihy2 = 1.0 / (hy * hy);
+      c.ihz2 = 1.0 / (hz * hz);
+      c.ry = (h * h) / (hy * hy);
+      c.rz = (h * h) / (hz * hz);
+    }
+    c.box = p.is_box() || force_box;
     return c;
   }
 };

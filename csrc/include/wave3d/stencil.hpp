@@ -30,6 +30,30 @@ W3D_HD double d2sum(double c, double xm, double xp, double ym, double yp, double
 #endif
 }
 
+// The same sum on a rectangular box (h_d = L_d/N): h_x²·Δ_h u = d_x + ry·d_y + rz·d_z with ry = h_x²/h_y², rz = h_x²/h_z²
+// (Coeffs), each difference taken exactly as above and combined as fma(rz, d_z, fma(ry, d_y, d_x)); lam = τ²/h_x² stays
+// the single update coefficient. With ry = rz = 1 both fmas are exact-product additions, (d_x + d_y) + d_z rounded as
+// d2sum rounds it: the box form fed ratios of 1 reproduces the cube's bits. On the device the ratios are wave-uniform
+// kernel arguments (scalar registers): two v_add_f64 become two v_fma_f64 with a scalar operand.
+W3D_HD double d2sum_box(double c, double xm, double xp, double ym, double yp, double zm, double zp, double ry,
+                        double rz) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fma(rz, __builtin_fma(-2.0, c, zp) + zm,
+                       __builtin_fma(ry, __builtin_fma(-2.0, c, yp) + ym, __builtin_fma(-2.0, c, xp) + xm));
+#else
+  const double c2 = 2.0 * c;
+  return std::fma(rz, zp - c2 + zm, std::fma(ry, yp - c2 + ym, xp - c2 + xm));
+#endif
+}
+// (kernels with a compile-time box flag)
+template <bool BOX>
+W3D_HD double d2sum_t(double c, double xm, double xp, double ym, double yp, double zm, double zp, double ry, double rz) {
+  if constexpr (BOX)
+    return d2sum_box(c, xm, xp, ym, yp, zm, zp, ry, rz);
+  else
+    return d2sum(c, xm, xp, ym, yp, zm, zp);
+}
+
 // Leapfrog update u^{n+1} = 2u^n − u^{n−1} + τ² Δ_h u^n (report.pdf p.5 §2.2(3)), with s = d2sum and lam = τ²/h².
 // The τ²-term is fused: (2c − old) + lam·s rounded once (one v_fma_f64: 10 instead of 11 f64 operations per node and
 // step). Host and device round identically (std::fma is the IEEE fused operation); the printed 128³ / 512³ logs keep

@@ -76,20 +76,31 @@ PYBIND11_MODULE(_C, m) {
   m.doc() = "wave3d native runtime: CDNA4 HIP kernels, RCCL halo exchange, CPU/OpenMP path";
 
   py::class_<Problem>(m, "Problem")
-      .def(py::init([](i64 N, double tau, int K, double L) {
+      .def(py::init([](i64 N, double tau, int K, double L, double Ly, double Lz) {
              Problem p;
              p.N = N;
              p.tau = tau;
              p.K = K;
              p.L = L;
+             p.Ly = Ly;
+             p.Lz = Lz;
              p.validate();
              return p;
            }),
-           py::arg("N") = 512, py::arg("tau") = 1e-3, py::arg("K") = 20, py::arg("L") = 1.0)
+           py::arg("N") = 512, py::arg("tau") = 1e-3, py::arg("K") = 20, py::arg("L") = 1.0, py::kw_only(),
+           py::arg("Ly") = 0.0, py::arg("Lz") = 0.0)
       .def_readwrite("N", &Problem::N)
       .def_readwrite("tau", &Problem::tau)
       .def_readwrite("K", &Problem::K)
       .def_readwrite("L", &Problem::L)
+      .def_readwrite("Ly", &Problem::Ly)
+      .def_readwrite("Lz", &Problem::Lz)
+      .def_property_readonly("edges",
+                             [](const Problem& p) { return py::make_tuple(p.L, p.edge_y(), p.edge_z()); })
+      .def_property_readonly("is_box", &Problem::is_box)
+      .def_property_readonly("hx", &Problem::hx)
+      .def_property_readonly("hy", &Problem::hy)
+      .def_property_readonly("hz", &Problem::hz)
       .def_property_readonly("h", &Problem::h)
       .def_property_readonly("a_t", &Problem::a_t)
       .def_property_readonly("courant", &Problem::courant)
@@ -98,18 +109,22 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("cell_updates", &Problem::cell_updates)
       .def("__repr__", [](const Problem& p) {
         return "Problem(N=" + std::to_string(p.N) + ", tau=" + std::to_string(p.tau) + ", K=" + std::to_string(p.K) +
-               ", L=" + std::to_string(p.L) + ")";
+               ", L=" + std::to_string(p.L) +
+               (p.is_box() ? ", Ly=" + std::to_string(p.edge_y()) + ", Lz=" + std::to_string(p.edge_z()) : "") + ")";
       });
 
   py::class_<Coeffs>(m, "Coeffs")
-      .def_static("from_problem", &Coeffs::from)
+      .def_static("from_problem", &Coeffs::from, py::arg("problem"), py::arg("force_box") = false)
       .def_readonly("ihx2", &Coeffs::ihx2)
       .def_readonly("ihy2", &Coeffs::ihy2)
       .def_readonly("ihz2", &Coeffs::ihz2)
       .def_readonly("tau2", &Coeffs::tau2)
       .def_readonly("half_tau2", &Coeffs::half_tau2)
       .def_readonly("lam", &Coeffs::lam)
-      .def_readonly("half_lam", &Coeffs::half_lam);
+      .def_readonly("half_lam", &Coeffs::half_lam)
+      .def_readonly("ry", &Coeffs::ry)
+      .def_readonly("rz", &Coeffs::rz)
+      .def_readonly("box", &Coeffs::box);
 
   m.def("sin_table_ext", [](const Problem& p) {
     auto v = sin_table_ext(p);

@@ -40,8 +40,10 @@ void cpu_init_first(const Layout& l, const Coeffs& c, const double* s, double* u
         u0[o] = v;
         const bool interior = gx > 0 && gx < N && gy > 0 && gy < N && gz > 0 && gz < N;
         if (interior) {
-          const double lap = d2sum(v, phi(s, gx - 1, gy, gz), phi(s, gx + 1, gy, gz), phi(s, gx, gy - 1, gz),
-                                  phi(s, gx, gy + 1, gz), phi(s, gx, gy, gz - 1), phi(s, gx, gy, gz + 1));
+          const double xm = phi(s, gx - 1, gy, gz), xp = phi(s, gx + 1, gy, gz), ym = phi(s, gx, gy - 1, gz),
+                       yp = phi(s, gx, gy + 1, gz), zm = phi(s, gx, gy, gz - 1), zp = phi(s, gx, gy, gz + 1);
+          const double lap =
+              c.box ? d2sum_box(v, xm, xp, ym, yp, zm, zp, c.ry, c.rz) : d2sum(v, xm, xp, ym, yp, zm, zp);
           u1[o] = first_step(v, lap, c.half_lam);
         } else {
           u1[o] = 0.0;
@@ -53,7 +55,7 @@ void cpu_init_first(const Layout& l, const Coeffs& c, const double* s, double* u
 
 namespace {
 
-template <bool CHECK>
+template <bool CHECK, bool BOX>
 void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* out, const LBox& b, const double* s,
                    double ct, ErrAcc* acc) {
   const i64 nxp = b.x1 - b.x0;
@@ -70,8 +72,8 @@ void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* 
       double* orow = out + row;
       for (i64 iz = b.z0; iz < b.z1; ++iz) {
         const double u = cr[iz];
-        const double lap =
-            d2sum(u, cr[iz - P], cr[iz + P], cr[iz - R], cr[iz + R], cr[iz - 1], cr[iz + 1]);
+        const double lap = d2sum_t<BOX>(u, cr[iz - P], cr[iz + P], cr[iz - R], cr[iz + R], cr[iz - 1], cr[iz + 1],
+                                        c.ry, c.rz);
         const double v = leapfrog(u, orow[iz], lap, c.lam);
         orow[iz] = v;
         if (CHECK) {
@@ -96,10 +98,16 @@ void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* 
 void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox& box,
                   const double* s, double ct, ErrAcc* acc) {
   if (box.empty()) return;
-  if (acc)
-    leapfrog_impl<true>(l, c, cur, old_out, box, s, ct, acc);
-  else
-    leapfrog_impl<false>(l, c, cur, old_out, box, s, ct, nullptr);
+  if (c.box) {  // (a rectangular box: stencil.hpp::d2sum_box)
+    if (acc)
+      leapfrog_impl<true, true>(l, c, cur, old_out, box, s, ct, acc);
+    else
+      leapfrog_impl<false, true>(l, c, cur, old_out, box, s, ct, nullptr);
+  } else if (acc) {
+    leapfrog_impl<true, false>(l, c, cur, old_out, box, s, ct, acc);
+  } else {
+    leapfrog_impl<false, false>(l, c, cur, old_out, box, s, ct, nullptr);
+  }
 }
 
 void cpu_error(const Layout& l, const double* u, const LBox& b, const double* s, double ct, ErrAcc* acc) {

@@ -45,6 +45,8 @@ struct Init2Params {
   i64 cx0, cx1, cy0, cy1, czo0, czo1;  // owned compute box (error check)
   i64 pz0, pz_end;
   double ihx2, ihy2, ihz2, half_tau2, tau2, ct2;
+  // rectangular box: h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box; 1 for a cube — the same bits as d2sum)
+  double ry, rz;
   int ntz, nty, xchunk, ntiles, nblocks;
 };
 
@@ -110,8 +112,8 @@ __global__ __launch_bounds__(64 * kWaves) void k_init_two(const Init2Params p) {
       for (int e = 0; e < 2; ++e) {
         const double zc = Z[e + 1];
         const double v = (xc * yc) * zc;
-        const double lap = d2sum(v, (xm * yc) * zc, (xp * yc) * zc, (xc * ym) * zc, (xc * yp) * zc, (xc * yc) * Z[e],
-                                (xc * yc) * Z[e + 2]);
+        const double lap = d2sum_box(v, (xm * yc) * zc, (xp * yc) * zc, (xc * ym) * zc, (xc * yp) * zc, (xc * yc) * Z[e],
+                                (xc * yc) * Z[e + 2], p.ry, p.rz);
         const bool in = xi && yi[j] && (e == 0 ? zi0 : zi1);
         r[e] = in ? first_step(v, lap, p.half_tau2) : 0.0;
       }
@@ -139,8 +141,8 @@ __global__ __launch_bounds__(64 * kWaves) void k_init_two(const Init2Params p) {
       const double zm = __shfl_up(uc[j].y, 1, 64);
       const double zp = __shfl_down(uc[j].x, 1, 64);
       v2d u2v;
-      const double l0 = d2sum(uc[j].x, um[j].x, up[j].x, uc[j - 1].x, uc[j + 1].x, zm, uc[j].y);
-      const double l1 = d2sum(uc[j].y, um[j].y, up[j].y, uc[j - 1].y, uc[j + 1].y, uc[j].x, zp);
+      const double l0 = d2sum_box(uc[j].x, um[j].x, up[j].x, uc[j - 1].x, uc[j + 1].x, zm, uc[j].y, p.ry, p.rz);
+      const double l1 = d2sum_box(uc[j].y, um[j].y, up[j].y, uc[j - 1].y, uc[j + 1].y, uc[j].x, zp, p.ry, p.rz);
       const double yc = Y[j + 1];
       const double u00 = (xc * yc) * Z[1], u01 = (xc * yc) * Z[2];  // u⁰ = φ
       const bool in = xi && yi[j];
@@ -218,6 +220,8 @@ Init2Params make_params(const Layout& l, const Coeffs& c) {
   p.ihz2 = c.ihz2;
   p.half_tau2 = c.half_lam;  // (the update coefficients of d2sum: τ²/(2h²), τ²/h²)
   p.tau2 = c.lam;
+  p.ry = c.ry;
+  p.rz = c.rz;
   const i64 nxb = p.x1 - p.x0, nyb = p.y1 - p.y0;
   if (nxb <= 0 || nyb <= 0 || p.pz_end <= p.pz0) return p;  // nothing to write
   p.ntz = static_cast<int>(ceil_div(p.pz_end - p.pz0, kOutPairs));

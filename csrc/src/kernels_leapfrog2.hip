@@ -61,6 +61,8 @@ struct Lf2Params {
   i64 sx0, sx1;                  // x range where stage-1 values are real (beyond: Dirichlet 0)
   i64 pz0, pz_end;
   double ihx2, ihy2, ihz2, tau2, ct2;
+  // rectangular box: h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box; 1 for a cube — the same bits as d2sum)
+  double ry, rz;
   int ntz, nty, xchunk, ntiles, nblocks, xcd_remap;
 };
 
@@ -185,8 +187,8 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC
       const v2d ym = c[e - 1], yp = c[e + 1];
       const double zm = __shfl_up(c[e].y, 1, 64);
       const double zp = __shfl_down(c[e].x, 1, 64);
-      const double l0 = d2sum(c[e].x, m[e].x, q[e].x, ym.x, yp.x, zm, c[e].y);
-      const double l1 = d2sum(c[e].y, m[e].y, q[e].y, ym.y, yp.y, c[e].x, zp);
+      const double l0 = d2sum_box(c[e].x, m[e].x, q[e].x, ym.x, yp.x, zm, c[e].y, p.ry, p.rz);
+      const double l1 = d2sum_box(c[e].y, m[e].y, q[e].y, ym.y, yp.y, c[e].x, zp, p.ry, p.rz);
       const bool keep = xin && ri[e];
       a[e].x = keep && in0 ? leapfrog(c[e].x, o[e].x, l0, tau2) : 0.0;
       a[e].y = keep && in1 ? leapfrog(c[e].y, o[e].y, l1, tau2) : 0.0;
@@ -208,8 +210,8 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC
         const v2d ctr = w1[e];
         const double zm = __shfl_up(ctr.y, 1, 64);
         const double zp = __shfl_down(ctr.x, 1, 64);
-        const double l0 = d2sum(ctr.x, w2[e].x, a[e].x, w1[e - 1].x, w1[e + 1].x, zm, ctr.y);
-        const double l1 = d2sum(ctr.y, w2[e].y, a[e].y, w1[e - 1].y, w1[e + 1].y, ctr.x, zp);
+        const double l0 = d2sum_box(ctr.x, w2[e].x, a[e].x, w1[e - 1].x, w1[e + 1].x, zm, ctr.y, p.ry, p.rz);
+        const double l1 = d2sum_box(ctr.y, w2[e].y, a[e].y, w1[e - 1].y, w1[e + 1].y, ctr.x, zp, p.ry, p.rz);
         v2d v;
         v.x = leapfrog(ctr.x, m[e].x, l0, tau2);
         v.y = leapfrog(ctr.y, m[e].y, l1, tau2);
@@ -364,6 +366,8 @@ void launch_leapfrog2(const Layout& l, const Coeffs& c, const double* prev, cons
   p.ihy2 = c.ihy2;
   p.ihz2 = c.ihz2;
   p.tau2 = c.lam;  // τ²/h², the coefficient of d2sum
+  p.ry = c.ry;
+  p.rz = c.rz;
   p.ct2 = ct2;
   const bool check = partials != nullptr;
   switch (t.rows) {

@@ -264,6 +264,10 @@ void leapfrog_p2_prepare() {
   prepare_p2_s3();
   prepare_p2_s4();
   prepare_p2_s5();
+  prepare_p2_box_s2();
+  prepare_p2_box_s3();
+  prepare_p2_box_s4();
+  prepare_p2_box_s5();
 }
 
 void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
@@ -289,6 +293,8 @@ void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const double* pr
   p.s = d_s;
   p.tau2 = c.lam;
   p.half_tau2 = c.half_lam;
+  p.ry = c.ry;
+  p.rz = c.rz;
   p.check_mask = partials != nullptr ? (check_mask & ((1 << t.stages) - 1)) : 0;
   p.partials = p.check_mask != 0 ? partials : nullptr;
   W3D_REQUIRE(level_stride == 0 || level_stride >= pl.nblocks, "leapfrog_p2: level stride below the block count");
@@ -297,11 +303,20 @@ void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const double* pr
 #ifdef W3D_EXPERIMENT_WGTIME
   p.wgtime = wgtime_slot(pl.nblocks, t.stages, analytic_start);
 #endif
-  switch (t.stages) {
-    case 2: launch_p2_s2(p, pl.nblocks, analytic_start, stream); break;
-    case 3: launch_p2_s3(p, pl.nblocks, analytic_start, stream); break;
-    case 4: launch_p2_s4(p, pl.nblocks, analytic_start, stream); break;
-    default: launch_p2_s5(p, pl.nblocks, analytic_start, stream); break;
+  if (c.box) {  // (a rectangular box: the BOX instantiations; a cube launches exactly what it always did)
+    switch (t.stages) {
+      case 2: launch_p2_box_s2(p, pl.nblocks, analytic_start, stream); break;
+      case 3: launch_p2_box_s3(p, pl.nblocks, analytic_start, stream); break;
+      case 4: launch_p2_box_s4(p, pl.nblocks, analytic_start, stream); break;
+      default: launch_p2_box_s5(p, pl.nblocks, analytic_start, stream); break;
+    }
+  } else {
+    switch (t.stages) {
+      case 2: launch_p2_s2(p, pl.nblocks, analytic_start, stream); break;
+      case 3: launch_p2_s3(p, pl.nblocks, analytic_start, stream); break;
+      case 4: launch_p2_s4(p, pl.nblocks, analytic_start, stream); break;
+      default: launch_p2_s5(p, pl.nblocks, analytic_start, stream); break;
+    }
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) fail(std::string("leapfrog_p2 launch: ") + hipGetErrorString(e));

@@ -55,6 +55,7 @@ void l2_flush_all(hipStream_t stream) {
 void leapfrog_tb_prepare(bool push) {
   leapfrog_p2_prepare();
   if (push) prepare_push();
+  prepare_box();
   prepare_nt<2, 768, false>();
   prepare_nt<3, 768, false>();
   prepare_nt<4, 768, false>();
@@ -139,6 +140,8 @@ void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const double* prev, co
   p.ihz2 = c.ihz2;
   p.tau2 = c.lam;  // τ²/h² and τ²/(2h²): the coefficients of d2sum
   p.half_tau2 = c.half_lam;
+  p.ry = c.ry;
+  p.rz = c.rz;
   p.check_mask = partials != nullptr ? (check_mask & ((1 << t.stages) - 1)) : 0;
   p.partials = p.check_mask != 0 ? partials : nullptr;
   W3D_REQUIRE(level_stride == 0 || level_stride >= pl.nblocks, "leapfrog_tb: level stride below the block count");
@@ -148,7 +151,11 @@ void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const double* prev, co
     W3D_REQUIRE(push->done_target % static_cast<unsigned>(pl.nblocks) == 0,
                 "leapfrog_tb push: done_target must be a multiple of the grid");
   if (push != nullptr && push->on) {
+    W3D_REQUIRE(!c.box, "leapfrog_tb push: the push transport has no rectangular-box kernels (cube domains only; use "
+                        "another transport for --box)");
     launch_push(p, pl.nblocks, t.stages, analytic_start, t.init_threads, stream);
+  } else if (c.box) {
+    launch_box(p, pl.nblocks, t, analytic_start, stream);
   } else {
     switch (t.stages) {
       case 2: launch_s<2, false>(p, pl.nblocks, t, analytic_start, stream); break;

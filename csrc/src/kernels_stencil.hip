@@ -66,6 +66,8 @@ struct InitParams {
   i64 plane, N, nx, ny, nz, gx0, gy0, gz0, zs, xg, yg, zg;
   int pairs_per_row, pairs_per_plane;
   double ihx2, ihy2, ihz2, half_tau2;
+  // rectangular box: h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box; 1 for a cube — the same bits as d2sum)
+  double ry, rz;
 };
 
 __global__ __launch_bounds__(256) void k_init_first(const InitParams p) {
@@ -90,8 +92,8 @@ __global__ __launch_bounds__(256) void k_init_first(const InitParams p) {
         gz <= p.N) {
       v = phi(s, gx, gy, gz);
       if (xy_in && gz > 0 && gz < p.N) {
-        const double lap = d2sum(v, phi(s, gx - 1, gy, gz), phi(s, gx + 1, gy, gz), phi(s, gx, gy - 1, gz),
-                                phi(s, gx, gy + 1, gz), phi(s, gx, gy, gz - 1), phi(s, gx, gy, gz + 1));
+        const double lap = d2sum_box(v, phi(s, gx - 1, gy, gz), phi(s, gx + 1, gy, gz), phi(s, gx, gy - 1, gz),
+                                phi(s, gx, gy + 1, gz), phi(s, gx, gy, gz - 1), phi(s, gx, gy, gz + 1), p.ry, p.rz);
         w = first_step(v, lap, p.half_tau2);
       }
     }
@@ -126,6 +128,8 @@ struct LfParams {
   Partial* partials;
   i64 plane, pitch, gx0, gy0, gz0, zs;
   double ihx2, ihy2, ihz2, tau2, ct;
+  // rectangular box: h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box; 1 for a cube — the same bits as d2sum)
+  double ry, rz;
   int nbox, ntiles, nblocks, xcd_remap;
   TileBox box[kMaxBoxes];
 };
@@ -234,8 +238,8 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
       const v2d yp = lds[buf][row + 2][lane + 1];
       const double zm = lds[buf][row + 1][lane].y;
       const double zp = lds[buf][row + 1][lane + 2].x;
-      const double l0 = d2sum(uc.x, um.x, up.x, ym.x, yp.x, zm, uc.y);
-      const double l1 = d2sum(uc.y, um.y, up.y, ym.y, yp.y, uc.x, zp);
+      const double l0 = d2sum_box(uc.x, um.x, up.x, ym.x, yp.x, zm, uc.y, p.ry, p.rz);
+      const double l1 = d2sum_box(uc.y, um.y, up.y, ym.y, yp.y, uc.x, zp, p.ry, p.rz);
       v2d r;
       r.x = leapfrog(uc.x, uo.x, l0, tau2);
       r.y = leapfrog(uc.y, uo.y, l1, tau2);
@@ -422,8 +426,8 @@ __global__ __launch_bounds__(64 * kWavesRq) __attribute__((amdgpu_waves_per_eu(R
         const double hzs = npe == 1 ? __shfl_down(hz[r], 1, 64) : hz[r];
         const double zm = lane == 0 ? hz[r] : up_y;
         const double zp = lane == npe - 1 ? hzs : dn_x;
-        const double l0 = d2sum(c[r].x, m[r].x, q[r].x, ym.x, yp.x, zm, c[r].y);
-        const double l1 = d2sum(c[r].y, m[r].y, q[r].y, ym.y, yp.y, c[r].x, zp);
+        const double l0 = d2sum_box(c[r].x, m[r].x, q[r].x, ym.x, yp.x, zm, c[r].y, p.ry, p.rz);
+        const double l1 = d2sum_box(c[r].y, m[r].y, q[r].y, ym.y, yp.y, c[r].x, zp, p.ry, p.rz);
         v2d v;
         v.x = leapfrog(c[r].x, o[r].x, l0, tau2);
         v.y = leapfrog(c[r].y, o[r].y, l1, tau2);
@@ -691,6 +695,8 @@ InitParams init_params(const Layout& l, const Coeffs& c, const double* d_s, doub
   p.ihy2 = c.ihy2;
   p.ihz2 = c.ihz2;
   p.half_tau2 = c.half_lam;  // τ²/(2h²), the coefficient of d2sum
+  p.ry = c.ry;
+  p.rz = c.rz;
   return p;
 }
 }  // namespace
@@ -720,6 +726,8 @@ void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double
   p.ihy2 = c.ihy2;
   p.ihz2 = c.ihz2;
   p.tau2 = c.lam;  // τ²/h², the coefficient of d2sum
+  p.ry = c.ry;
+  p.rz = c.rz;
   p.ct = ct;
   const bool check = partials != nullptr;
   if (t.variant == 1) {

@@ -24,7 +24,10 @@ void write_dump(const std::string& prefix, const Problem& p, const Layout& l, co
   std::ofstream j(base + ".json", std::ios::trunc);
   j.precision(17);
   j << "{\"format\": \"wave3d-dump-v1\", \"dtype\": \"float64\", \"order\": \"C\", \"N\": " << p.N
-    << ", \"L\": " << p.L << ", \"tau\": " << p.tau << ", \"step\": " << step << ", \"t\": " << step * p.tau
+    << ", \"L\": " << p.L;
+  // (a rectangular box: its three edges under a key of their own; a cube's sidecar is what it always was)
+  if (p.is_box()) j << ", \"box\": [" << p.L << ", " << p.edge_y() << ", " << p.edge_z() << "]";
+  j << ", \"tau\": " << p.tau << ", \"step\": " << step << ", \"t\": " << step * p.tau
     << ", \"shape\": [" << l.nx << ", " << l.ny << ", " << l.nz << "], \"offset\": [" << l.gx0 << ", " << l.gy0
     << ", " << l.gz0 << "], \"global_shape\": [" << p.N + 1 << ", " << p.N + 1 << ", " << p.N + 1
     << "], \"rank\": " << rank << ", \"world\": " << world << ", \"dims\": [" << d.px << ", " << d.py << ", " << d.pz
@@ -92,6 +95,16 @@ int load_dump_global(const std::string& prefix, const Problem& p, std::vector<do
       const std::vector<double> v = json_numbers(m, key);
       W3D_REQUIRE(v.size() == 1 && std::fabs(v[0] - want) <= 1e-15 * std::fabs(want),
                   std::string("resume: dump ") + key + " differs from the run's " + key);
+    }
+    // (the box: a sidecar without the key is a cube of edge L, as every dump written before boxes existed)
+    {
+      const std::vector<double> bx = json_numbers(m, "box"), ll = json_numbers(m, "L");
+      W3D_REQUIRE(bx.empty() || bx.size() == 3, "resume: bad box in sidecar " + b);
+      const double have[3] = {bx.empty() ? ll[0] : bx[0], bx.empty() ? ll[0] : bx[1], bx.empty() ? ll[0] : bx[2]};
+      const double want[3] = {p.L, p.edge_y(), p.edge_z()};
+      for (int a = 0; a < 3; ++a)
+        W3D_REQUIRE(std::fabs(have[a] - want[a]) <= 1e-15 * std::fabs(want[a]),
+                    "resume: dump box differs from the run's box");
     }
     W3D_REQUIRE(step < 0 || step == static_cast<int>(st[0]), "resume: rank dumps of different steps");
     step = static_cast<int>(st[0]);

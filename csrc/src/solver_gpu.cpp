@@ -154,6 +154,9 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
   if (const char* v = std::getenv("W3D_TB_MINCHUNK")) o.tiling_tb.min_chunk = std::atoi(v);
   if (const char* v = std::getenv("W3D_TB_XCDBLOCKS")) o.tiling_tb.xcd_blocks = *v == '1';
   if (const char* v = std::getenv("W3D_TB_XCDREMAP")) o.tiling_tb.xcd_remap = *v == '1';  // (A/B runs)
+  // (the push transport's kernels exist for cubes only: kernels_leapfrog_tb_push.hip)
+  W3D_REQUIRE(!(o.push && world > 1 && coef_.box),
+              "the push transport has no rectangular-box kernels: run a --box problem over rccl or sdma");
   W3D_REQUIRE(world == 1 || comm_ || loopback_ || o.fake_comm || ((o.push || o.sdma) && o.push_no_collective),
               "world > 1 needs an RCCL communicator (or the loopback group, or the push / sdma transport without one)");
   size_t free_b = 0, total_b = 0;

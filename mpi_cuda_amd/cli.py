@@ -26,7 +26,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("N", type=int, help="intervals per axis ((N+1)^3 nodes)")
     ap.add_argument("tau", type=float, help="time step")
     ap.add_argument("K", type=int, help="number of steps")
-    ap.add_argument("L", type=float, nargs="?", default=1.0, help="cube edge (default 1)")
+    ap.add_argument("L", type=float, nargs="?", default=None, help="cube edge (default 1)")
+    ap.add_argument("--box", default="", metavar="LX,LY,LZ",
+                    help="rectangular box [0,LX]x[0,LY]x[0,LZ], the same N per axis (excludes the positional L)")
     ap.add_argument("--backend", default="auto", choices=["auto", "hip", "cpu", "torch"])
     ap.add_argument("--transport", default="auto", choices=["auto", "rccl", "torch", "loopback", "rccl-self", "push",
                                                                "push-ipc", "sdma", "sdma-ipc", "native", "none"])
@@ -53,7 +55,21 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None) -> int:
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    box = None
+    if a.box:
+        if a.L is not None:
+            ap.error("--box and the positional L exclude each other")
+        try:
+            box = tuple(float(v) for v in a.box.split(","))
+        except ValueError:
+            box = ()
+        if len(box) != 3 or not all(e > 0 and math.isfinite(e) for e in box):
+            ap.error("--box expects three positive edges LX,LY,LZ")
+        a.L = box[0]
+    elif a.L is None:
+        a.L = 1.0
     import torch
     import torch.distributed as dist
 
@@ -63,10 +79,13 @@ def main(argv=None) -> int:
     from .utils import dump as dumpio
     from .utils.report import gcell_per_s
 
-    spec = ProblemSpec(N=a.N, tau=a.tau, K=a.K, L=a.L, check_every=a.check_every)
+    spec = ProblemSpec(N=a.N, tau=a.tau, K=a.K, L=a.L, check_every=a.check_every,
+                       Ly=box[1] if box else None, Lz=box[2] if box else None)
+    box_note = " box=" + ",".join(f"{e:g}" for e in spec.edges) if spec.is_box else ""
     if not spec.cfl_ok:
-        print(f"wave3d: CFL violated: courant = tau*sqrt(3)/h = {spec.courant:.4f} > 1 (tau_max = {spec.tau_max:.3e})",
-              file=sys.stderr)
+        form = "tau*sqrt(1/hx^2+1/hy^2+1/hz^2)" if spec.is_box else "tau*sqrt(3)/h"
+        print(f"wave3d: CFL violated: courant = {form} = {spec.courant:.4f} > 1 (tau_max = {spec.tau_max:.3e}"
+              f"{' for' + box_note if box_note else ''})", file=sys.stderr)
         if not a.force:
             return 2
     backend = a.backend
@@ -92,6 +111,10 @@ def main(argv=None) -> int:
                 if got is None or not math.isclose(float(got), float(want), rel_tol=1e-15, abs_tol=0.0):
                     print(f"wave3d: resume: checkpoint {key} = {got} differs from the run's {want}", file=sys.stderr)
                     return 2
+            if any(not math.isclose(g, w, rel_tol=1e-15, abs_tol=0.0) for g, w in zip(dumpio.box_of(m), spec.edges)):
+                print(f"wave3d: resume: checkpoint box {list(dumpio.box_of(m))} differs from the run's "
+                      f"{list(spec.edges)}", file=sys.stderr)
+                return 2
         s.set_state(prev, cur, int(meta_c["step"]))
     r = None
     times = []
@@ -108,7 +131,7 @@ def main(argv=None) -> int:
     best = float(t[0])
     if rank == 0:
         if not a.quiet:
-            print(f"wave3d: N={a.N} tau={a.tau:g} K={a.K} L={a.L:g} backend={s.backend} transport={s.transport} "
+            print(f"wave3d: N={a.N} tau={a.tau:g} K={a.K} L={a.L:g}{box_note} backend={s.backend} transport={s.transport} "
                   f"ranks={s.world} decomp={'x'.join(map(str, s.dims))}")
             for line in r.lines():
                 print(line)
@@ -120,7 +143,7 @@ def main(argv=None) -> int:
         if a.json:
             with open(a.json, "w") as f:
                 json.dump({"backend": s.backend, "transport": s.transport, "N": a.N, "tau": a.tau, "K": a.K, "L": a.L,
-                           "ranks": s.world, "dims": list(s.dims), "solve_s": best,
+                           **({"box": list(spec.edges)} if spec.is_box else {}), "ranks": s.world, "dims": list(s.dims), "solve_s": best,
                            "gcell_per_s": gcell_per_s(a.N, a.K, best),
                            "steps": [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]}, f)
     if a.dump or a.checkpoint:
@@ -128,12 +151,12 @@ def main(argv=None) -> int:
             if s.transport in ("loopback", "rccl-self", "push", "sdma"):
                 if rank == 0:
                     dumpio.save(prefix, s.global_field(which).numpy(), N=a.N, L=a.L, tau=a.tau,
-                                step=a.K - which)
+                                step=a.K - which, box=spec.edges)
                 return
             f = s.owned_field(which)
             off = s.native.plan.box[0::2] if s.transport == "torch" else (0, 0, 0)
             dumpio.save(prefix, f.numpy(), N=a.N, L=a.L, tau=a.tau, step=a.K - which, offset=off, rank=rank,
-                        world=s.world, dims=s.dims)
+                        world=s.world, dims=s.dims, box=spec.edges)
 
         if a.dump:
             write(a.dump, 0)

@@ -9,6 +9,8 @@ Reference behaviour (AICCer1/MPI-CUDA; the programs are not in the snapshot, the
   u¹ = u⁰ + τ²/2·Δ_h u⁰                                                                        report.pdf p.5 §2-2.2
 * "Max Error" = L∞ over the nodes, "L2 Error" = RMS over the (N−1)³ interior nodes           report.pdf p.6 §3.1.2,
                                                                                                SURVEY.md §1.3 VERIFIED
+* rectangular box [0,Lx]×[0,Ly]×[0,Lz], same N per axis: u_a = Π_d sin(π x_d/L_d)·cos(a_t t),
+  a_t = π·√(1/Lx²+1/Ly²+1/Lz²), h_d = L_d/N (``ProblemSpec(Ly=, Lz=)``; L is Lx)                   report.pdf p.4 §1
 * golden log (512³, τ=1e-3, K=20, L=1)                                                        report.pdf p.15-16 §4.3
 
 The closed-form oracle: φ is a discrete eigenfunction of Δ_h with eigenvalue −λ, so the discrete
@@ -41,7 +43,10 @@ REFERENCE_LOG_512 = [
 
 @dataclass
 class ProblemSpec:
-    """N intervals per axis ((N+1)³ nodes), time step tau, K steps, cube edge L (positional CLI ``N tau K [L]``)."""
+    """N intervals per axis ((N+1)³ nodes), time step tau, K steps, cube edge L (positional CLI ``N tau K [L]``).
+
+    ``Ly`` / ``Lz`` make the domain a rectangular box Lx × Ly × Lz with Lx = L (CLI ``--box LX,LY,LZ``); None means
+    "= L". A spec whose three edges are equal is a cube and evaluates exactly the cube's expressions."""
 
     N: int = 512
     tau: float = 1e-3
@@ -49,6 +54,8 @@ class ProblemSpec:
     L: float = 1.0
     check_every: int = 2
     extra: dict = field(default_factory=dict)
+    Ly: float | None = None
+    Lz: float | None = None
 
     def __post_init__(self) -> None:
         if self.N < 2:
@@ -59,18 +66,58 @@ class ProblemSpec:
             raise ValueError("K must be >= 1")
         if not (self.L > 0 and math.isfinite(self.L)):
             raise ValueError("L must be > 0")
+        for name in ("Ly", "Lz"):
+            v = getattr(self, name)
+            if v is not None and not (v > 0 and math.isfinite(v)):
+                raise ValueError(f"{name} must be > 0")
+
+    @property
+    def edges(self) -> tuple[float, float, float]:
+        """(Lx, Ly, Lz)."""
+        return (self.L, self.L if self.Ly is None else float(self.Ly), self.L if self.Lz is None else float(self.Lz))
+
+    @property
+    def is_box(self) -> bool:
+        lx, ly, lz = self.edges
+        return ly != lx or lz != lx
 
     @property
     def h(self) -> float:
+        """h_x (a cube's only step)."""
         return self.L / self.N
 
     @property
+    def hs(self) -> tuple[float, float, float]:
+        """(h_x, h_y, h_z)."""
+        lx, ly, lz = self.edges
+        return (lx / self.N, ly / self.N, lz / self.N)
+
+    @property
+    def inv_h2_sum(self) -> float:
+        """Σ_d 1/h_d², summed as (x + y) + z (problem.hpp::Problem::inv_h2_sum: the same bits)."""
+        hx, hy, hz = self.hs
+        return (1.0 / (hx * hx) + 1.0 / (hy * hy)) + 1.0 / (hz * hz)
+
+    @property
+    def ratios(self) -> tuple[float, float]:
+        """(ry, rz) = (h_x²/h_y², h_x²/h_z²), the weights of stencil.hpp::d2sum_box (problem.hpp::Coeffs)."""
+        if not self.is_box:
+            return (1.0, 1.0)
+        hx, hy, hz = self.hs
+        return ((hx * hx) / (hy * hy), (hx * hx) / (hz * hz))
+
+    @property
     def a_t(self) -> float:
-        return math.pi * math.sqrt(3.0 / (self.L * self.L))
+        if not self.is_box:
+            return math.pi * math.sqrt(3.0 / (self.L * self.L))
+        lx, ly, lz = self.edges
+        return math.pi * math.sqrt((1.0 / (lx * lx) + 1.0 / (ly * ly)) + 1.0 / (lz * lz))
 
     @property
     def courant(self) -> float:
-        """τ·√3/h — the 3-D 7-point leapfrog is stable iff this is ≤ 1."""
+        """τ·√(Σ 1/h_d²) (cube: τ·√3/h) — the 3-D 7-point leapfrog is stable iff this is ≤ 1."""
+        if self.is_box:
+            return self.tau * math.sqrt(self.inv_h2_sum)
         return self.tau * math.sqrt(3.0) / self.h
 
     @property
@@ -79,6 +126,8 @@ class ProblemSpec:
 
     @property
     def tau_max(self) -> float:
+        if self.is_box:
+            return 1.0 / math.sqrt(self.inv_h2_sum)
         return self.h / math.sqrt(3.0)
 
     @property
@@ -93,11 +142,19 @@ class ProblemSpec:
     def native(self):
         from .._native import load
 
-        return load().Problem(self.N, self.tau, self.K, self.L)
+        if self.Ly is None and self.Lz is None:
+            return load().Problem(self.N, self.tau, self.K, self.L)
+        _, ly, lz = self.edges
+        return load().Problem(self.N, self.tau, self.K, self.L, Ly=ly, Lz=lz)
 
     def as_dict(self) -> dict:
         d = asdict(self)
         d.pop("extra", None)
+        if self.Ly is None and self.Lz is None:  # (a cube's dictionary is what it always was)
+            d.pop("Ly")
+            d.pop("Lz")
+        else:
+            d["Ly"], d["Lz"] = self.edges[1], self.edges[2]
         return d
 
 
@@ -129,10 +186,16 @@ def oracle_errors(spec: ProblemSpec, steps: list[int] | None = None, dps: int = 
     L = mp.mpf(spec.L)
     h = L / N
     tau = mp.mpf(spec.tau)
-    lam = 3 * (4 / h**2) * mp.sin(mp.pi * h / (2 * L)) ** 2
+    if spec.is_box:
+        # λ_h = 4·sin²(π/(2N))·Σ_d 1/h_d²: the same sine table on every axis (sin(π i h_d/L_d) = sin(π i/N))
+        Ls = [mp.mpf(e) for e in spec.edges]
+        lam = 4 * mp.sin(mp.pi / (2 * N)) ** 2 * mp.fsum(1 / (e / N) ** 2 for e in Ls)
+        a_t = mp.pi * mp.sqrt(mp.fsum(1 / e**2 for e in Ls))
+    else:
+        lam = 3 * (4 / h**2) * mp.sin(mp.pi * h / (2 * L)) ** 2
+        a_t = mp.pi * mp.sqrt(3 / L**2)
     cos_theta = 1 - tau**2 * lam / 2
     theta = mp.acos(cos_theta)
-    a_t = mp.pi * mp.sqrt(3 / L**2)
     # max_i |sin(π i/N)|³ and Σ_interior φ² = (Σ_i sin²(π i/N))³
     s_max = max(abs(mp.sin(mp.pi * i / N)) for i in range(N + 1))
     s2 = mp.fsum(mp.sin(mp.pi * i / N) ** 2 for i in range(1, N))
@@ -147,13 +210,18 @@ def oracle_errors(spec: ProblemSpec, steps: list[int] | None = None, dps: int = 
 # ----------------------------------------------------------------------------------------------------------------
 # independent PyTorch fp64 reference solver (second oracle; runs on CPU or GPU)
 # ----------------------------------------------------------------------------------------------------------------
-def d2sum_torch(u: torch.Tensor) -> torch.Tensor:
-    """h²·Δ_h on the interior of a full node grid: the sum of the three second differences (stencil.hpp::d2sum, same
-    operation order as the native kernels)."""
+def d2sum_torch(u: torch.Tensor, ratios: tuple[float, float] | None = None) -> torch.Tensor:
+    """h_x²·Δ_h on the interior of a full node grid: the sum of the three second differences (stencil.hpp::d2sum, same
+    operation order as the native kernels). ``ratios`` = (ry, rz): the box form fma(rz, d_z, fma(ry, d_y, d_x))
+    (stencil.hpp::d2sum_box)."""
     c = u[1:-1, 1:-1, 1:-1]
     c2 = 2.0 * c
-    return ((u[2:, 1:-1, 1:-1] - c2 + u[:-2, 1:-1, 1:-1]) + (u[1:-1, 2:, 1:-1] - c2 + u[1:-1, :-2, 1:-1])
-            + (u[1:-1, 1:-1, 2:] - c2 + u[1:-1, 1:-1, :-2]))
+    dx = u[2:, 1:-1, 1:-1] - c2 + u[:-2, 1:-1, 1:-1]
+    dy = u[1:-1, 2:, 1:-1] - c2 + u[1:-1, :-2, 1:-1]
+    dz = u[1:-1, 1:-1, 2:] - c2 + u[1:-1, 1:-1, :-2]
+    if ratios is None:
+        return (dx + dy) + dz
+    return fma_torch(ratios[1], dz, fma_torch(ratios[0], dy, dx))
 
 
 def fma_torch(a: float, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
@@ -184,7 +252,8 @@ def torch_reference_solve(spec: ProblemSpec, device="cpu", return_fields: bool =
     u1 = torch.zeros_like(u0)
     ih2 = 1.0 / (spec.h * spec.h)
     lam, half_lam = tau2 * ih2, (0.5 * tau2) * ih2  # problem.hpp::Coeffs: the coefficients of d2sum
-    u1[1:-1, 1:-1, 1:-1] = fma_torch(half_lam, d2sum_torch(u0), u0[1:-1, 1:-1, 1:-1])
+    ratios = spec.ratios if spec.is_box else None
+    u1[1:-1, 1:-1, 1:-1] = fma_torch(half_lam, d2sum_torch(u0, ratios), u0[1:-1, 1:-1, 1:-1])
     denom = float(spec.N - 1) ** 3
     errs = {}
     checks = set(spec.check_steps())
@@ -199,7 +268,7 @@ def torch_reference_solve(spec: ProblemSpec, device="cpu", return_fields: bool =
     for n in range(1, spec.K):
         nxt = torch.zeros_like(cur)
         c = cur[1:-1, 1:-1, 1:-1]
-        nxt[1:-1, 1:-1, 1:-1] = fma_torch(lam, d2sum_torch(cur), 2.0 * c - prev[1:-1, 1:-1, 1:-1])
+        nxt[1:-1, 1:-1, 1:-1] = fma_torch(lam, d2sum_torch(cur, ratios), 2.0 * c - prev[1:-1, 1:-1, 1:-1])
         prev, cur = cur, nxt
         if n + 1 in checks:
             errs[n + 1] = err(cur, n + 1)

@@ -52,7 +52,10 @@ class NativeRankProcess:
 
                 nonce = broadcast_bytes(nonce.encode() if rank == 0 else None, 0, group).decode()
         tmp = tempfile.gettempdir()
-        cmd = [CLI, str(spec.N), repr(spec.tau), str(spec.K), repr(spec.L), "--serve", "--quiet",
+        # (a rectangular box goes as --box, which excludes the positional L; a cube's command line is what it was)
+        size = (["--box", ",".join(repr(float(e)) for e in spec.edges)] if getattr(spec, "is_box", False)
+                else [repr(spec.L)])
+        cmd = [CLI, str(spec.N), repr(spec.tau), str(spec.K), *size, "--serve", "--quiet",
                "--decomp", decomp, "--temporal", str(temporal), "--check-every", str(spec.check_every),
                *_TRANSPORT_FLAGS[transport]]
         if not overlap:

@@ -5,7 +5,8 @@ of a decomposed run:
 
 * ``.bin``  raw little-endian float64, C order [x][y][z], the rank's OWNED nodes only (shape = json "shape");
 * ``.json`` {"format": "wave3d-dump-v1", "dtype": "float64", "order": "C", "N", "L", "tau", "step", "t", "shape",
-  "offset" (global index of the first node), "global_shape" [(N+1)]*3, "rank", "world", "dims"}.
+  "offset" (global index of the first node), "global_shape" [(N+1)]*3, "rank", "world", "dims"}; a rectangular box
+  adds "box": [Lx, Ly, Lz] ("L" is Lx). The key is absent for cubes, so dumps written before boxes existed still load.
 
 A single-rank dump is the whole (N+1)³ field: ``numpy.fromfile(p + ".bin").reshape(N+1, N+1, N+1)``.
 ``load()`` assembles either kind; ``save()`` writes the same format from Python (used for checkpoints).
@@ -22,13 +23,15 @@ FORMAT = "wave3d-dump-v1"
 
 
 def save(prefix: str, field: np.ndarray, *, N: int, L: float, tau: float, step: int, offset=(0, 0, 0), rank: int = 0,
-         world: int = 1, dims=(1, 1, 1), extra: dict | None = None) -> None:
+         world: int = 1, dims=(1, 1, 1), extra: dict | None = None, box=None) -> None:
     field = np.ascontiguousarray(field, dtype="<f8")
     base = prefix if world == 1 else f"{prefix}.rank{rank}"
     field.tofile(base + ".bin")
     meta = {"format": FORMAT, "dtype": "float64", "order": "C", "N": int(N), "L": float(L), "tau": float(tau),
             "step": int(step), "t": float(step * tau), "shape": list(field.shape), "offset": [int(o) for o in offset],
             "global_shape": [N + 1] * 3, "rank": int(rank), "world": int(world), "dims": [int(d) for d in dims]}
+    if box is not None and not (box[0] == box[1] == box[2]):  # (absent for cubes, as in every earlier dump)
+        meta["box"] = [float(e) for e in box]
     if extra:
         meta.update(extra)
     with open(base + ".json", "w") as f:
@@ -51,6 +54,12 @@ def read_meta(prefix: str) -> list[dict]:
         m["_bin"] = p[:-5] + ".bin"
         metas.append(m)
     return metas
+
+
+def box_of(meta: dict) -> tuple[float, float, float]:
+    """(Lx, Ly, Lz) of a dump's sidecar: its "box", or the cube of edge "L"."""
+    b = meta.get("box")
+    return tuple(float(e) for e in b) if b else (float(meta["L"]),) * 3
 
 
 def load(prefix: str) -> tuple[np.ndarray, dict]:

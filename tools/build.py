@@ -56,6 +56,12 @@ LIB_SOURCES = [
     ("src/kernels_leapfrog_p2_s3.hip", "hip"),
     ("src/kernels_leapfrog_p2_s4.hip", "hip"),
     ("src/kernels_leapfrog_p2_s5.hip", "hip"),
+    # rectangular-box instantiations of the two LDS pass families (the cube's stay in the units above)
+    ("src/kernels_leapfrog_tb_box.hip", "hip"),
+    ("src/kernels_leapfrog_p2_box_s2.hip", "hip"),
+    ("src/kernels_leapfrog_p2_box_s3.hip", "hip"),
+    ("src/kernels_leapfrog_p2_box_s4.hip", "hip"),
+    ("src/kernels_leapfrog_p2_box_s5.hip", "hip"),
     ("src/solver_gpu.cpp", "hip"),
     ("src/capture_guard.cpp", "hip"),
     ("src/transport_sdma.cpp", "hip"),

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "wave3d/kernels.hpp"
+#include "wave3d/pass_grid.hpp"
 #include "wave3d/stencil.hpp"
 
 namespace wave3d {
@@ -891,18 +892,14 @@ inline TbPlan make_plan_tb(const Layout& l, const LBox& b, const LeapfrogTbTilin
   p.z0 = static_cast<int>(b.z0);
   p.z1 = static_cast<int>(b.z1);
   if (b.x1 <= b.x0 || b.y1 <= b.y0 || b.z1 <= b.z0) return pl;
-  p.nty = static_cast<int>(ceil_div(b.y1 - b.y0, kTile));
-  p.ntz = static_cast<int>(ceil_div(b.z1 - b.z0, kTile));
-  const int tiles = p.nty * p.ntz;
-  // x chunks when the tile grid alone leaves CUs idle (3-D block boxes): at least min_chunk planes per chunk
-  if (t.target_blocks > tiles) {
-    const i64 nxb = b.x1 - b.x0;
-    const i64 want = imin(ceil_div(t.target_blocks, tiles), imax(1, nxb / imax(1, t.min_chunk)));
-    p.xlen = static_cast<int>(ceil_div(nxb, imax(1, want)));
-    p.nxc = static_cast<int>(ceil_div(nxb, p.xlen));
-  }
-  const int blocks = tiles * p.nxc;
-  pl.nblocks = t.xcd_remap ? static_cast<int>(round_up(blocks, 8)) : blocks;
+  // the tile grid and the x chunks: the host-side arithmetic that also sizes the partial slots (pass_grid.hpp)
+  const PassBoxGrid g = tb_box_grid(b, t);
+  p.nty = g.nty;
+  p.ntz = g.ntz;
+  p.xlen = g.xlen;
+  p.nxc = g.nxc;
+  const int tiles = g.tiles();
+  pl.nblocks = tb_round(g.blocks(), t);
   p.nblocks = pl.nblocks;
   p.xcd_remap = t.xcd_remap ? 1 : 0;
   p.xper = pl.nblocks / 8;

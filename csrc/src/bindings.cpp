@@ -7,10 +7,13 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <tuple>
+
 #include "wave3d/capture_guard.hpp"
 #include "wave3d/cpu.hpp"
 #include "wave3d/decomp.hpp"
 #include "wave3d/kernels.hpp"
+#include "wave3d/pass_grid.hpp"
 #include "wave3d/problem.hpp"
 #include "wave3d/runtime.hpp"
 #include "wave3d/solver.hpp"
@@ -442,19 +445,94 @@ PYBIND11_MODULE(_C, m) {
   m.def("gpu_leapfrog_p2_supported", &leapfrog_p2_supported);
   m.def("gpu_leapfrog_tb_lds_bytes", &leapfrog_tb_lds_bytes);
   m.def("gpu_leapfrog_tb_partials", &leapfrog_tb_partials);
+  // pack_zf: the fused z-face pack (TbPack, k_leapfrog_tb only): device pointers of the four staging parts
+  // [low z u^{n+S}, low z u^{n+S−1}, high z u^{n+S}, high z u^{n+S−1}] (0: no such part), pack_w: the band width
   m.def("gpu_leapfrog_tb",
         [](const Layout& l, const Coeffs& c, std::uintptr_t prev, std::uintptr_t cur, std::uintptr_t out1,
            std::uintptr_t out2, const LBox& box, std::uintptr_t s, std::vector<double> ct, int check_mask,
            std::uintptr_t partials, const LeapfrogTbTiling& t, std::uintptr_t stream, const LBox& real,
-           bool analytic_start) {
+           bool analytic_start, int level_stride, int grid_blocks, const std::vector<std::uintptr_t>& pack_zf,
+           int pack_w) {
           ct.resize(5, 0.0);
-          launch_leapfrog_tb(l, c, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
-                             dptr<double>(out2), box, dptr<const double>(s) + 1, ct.data(), check_mask,
-                             dptr<Partial>(partials), t, sptr(stream), real, analytic_start);
+          if (pack_zf.empty()) {
+            launch_leapfrog_tb(l, c, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
+                               dptr<double>(out2), box, dptr<const double>(s) + 1, ct.data(), check_mask,
+                               dptr<Partial>(partials), t, sptr(stream), real, analytic_start, level_stride,
+                               grid_blocks);
+            return;
+          }
+          W3D_REQUIRE(pack_zf.size() == 4, "gpu_leapfrog_tb: pack_zf takes four pointers");
+          TbPack pk;
+          for (int side = 0; side < 2; ++side)
+            for (int f = 0; f < 2; ++f) pk.zf[side][f] = dptr<double>(pack_zf[static_cast<size_t>(2 * side + f)]);
+          pk.w = pack_w;
+          pk.ny = static_cast<int>(l.ny);
+          pk.nz = static_cast<int>(l.nz);
+          TbPack* dev = nullptr;
+          W3D_HIP(hipMalloc(&dev, sizeof(TbPack)));
+          try {
+            W3D_HIP(hipMemcpy(dev, &pk, sizeof(TbPack), hipMemcpyHostToDevice));
+            launch_leapfrog_tb(l, c, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
+                               dptr<double>(out2), box, dptr<const double>(s) + 1, ct.data(), check_mask,
+                               dptr<Partial>(partials), t, sptr(stream), real, analytic_start, level_stride,
+                               grid_blocks, nullptr, nullptr, &pk, dev);
+            W3D_HIP(hipStreamSynchronize(sptr(stream)));  // (the kernel reads the parameters from `dev`)
+          } catch (...) {
+            (void)hipFree(dev);
+            throw;
+          }
+          W3D_HIP(hipFree(dev));
         },
         py::arg("layout"), py::arg("coeffs"), py::arg("prev"), py::arg("cur"), py::arg("out1"), py::arg("out2"),
         py::arg("box"), py::arg("s"), py::arg("ct"), py::arg("check_mask"), py::arg("partials"), py::arg("tiling"),
-        py::arg("stream"), py::arg("real") = tb_default_real(), py::arg("analytic_start") = false);
+        py::arg("stream"), py::arg("real") = tb_default_real(), py::arg("analytic_start") = false,
+        py::arg("level_stride") = 0, py::arg("grid_blocks") = 0, py::arg("pack_zf") = std::vector<std::uintptr_t>{},
+        py::arg("pack_w") = 0);
+  m.def("gpu_leapfrog_p2_partials", &leapfrog_p2_partials);
+  m.def("gpu_leapfrog_p2_boxes",
+        [](const Layout& l, const Coeffs& c, std::uintptr_t prev, std::uintptr_t cur, std::uintptr_t out1,
+           std::uintptr_t out2, const std::vector<LBox>& boxes, std::uintptr_t s, std::vector<double> ct,
+           int check_mask, std::uintptr_t partials, const LeapfrogTbTiling& t, std::uintptr_t stream, const LBox& real,
+           bool analytic_start, int level_stride, int grid_blocks) {
+          ct.resize(5, 0.0);
+          launch_leapfrog_p2_boxes(l, c, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
+                                   dptr<double>(out2), boxes.data(), static_cast<int>(boxes.size()),
+                                   dptr<const double>(s) + 1, ct.data(), check_mask, dptr<Partial>(partials), t,
+                                   sptr(stream), real, analytic_start, level_stride, grid_blocks);
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("prev"), py::arg("cur"), py::arg("out1"), py::arg("out2"),
+        py::arg("boxes"), py::arg("s"), py::arg("ct"), py::arg("check_mask"), py::arg("partials"), py::arg("tiling"),
+        py::arg("stream"), py::arg("real") = tb_default_real(), py::arg("analytic_start") = false,
+        py::arg("level_stride") = 0, py::arg("grid_blocks") = 0,
+        "one pair-tiled launch over up to 6 boxes (the overlapped schedules' shells); their partials share one slot");
+  // the host-side workgroup arithmetic of the passes (pass_grid.hpp)
+  m.def("p2_launch_blocks", [](const std::vector<LBox>& boxes, const LeapfrogTbTiling& t) {
+    const P2LaunchGrid g = p2_launch_grid(boxes.data(), static_cast<int>(boxes.size()), t);
+    std::vector<std::tuple<int, int, int, int, int>> per;  // (nty, ntz, xlen, nxc, blk0) per box
+    for (int k = 0; k < g.nbox; ++k)
+      per.emplace_back(g.box[k].nty, g.box[k].ntz, g.box[k].xlen, g.box[k].nxc, g.box[k].blk0);
+    return py::make_tuple(g.nblocks, per);
+  });
+  m.def("tb_slot_blocks", &tb_slot_blocks);
+  m.def("tb_shells_launch_blocks", [](const Layout& l, const std::vector<LBox>& boxes, const LeapfrogTbTiling& t,
+                                      int slot) {
+    return tb_shells_launch_blocks(l, boxes.data(), static_cast<int>(boxes.size()), t, slot);
+  });
+  // S-deep exchange regions <-> staging (k_box_copy); the table handle is freed with free_box_copy_table
+  py::class_<BoxCopyTable>(m, "BoxCopyTable")
+      .def_readonly("njobs", &BoxCopyTable::njobs)
+      .def_readonly("nblocks", &BoxCopyTable::nblocks);
+  m.def("make_box_copy_table", &make_box_copy_table, py::arg("plan"), py::arg("recv_side"),
+        py::arg("skip_zfaces") = false);
+  m.def("free_box_copy_table", &free_box_copy_table);
+  m.def("launch_box_copy", [](const Layout& l, const BoxCopyTable& t, int mode, std::uintptr_t u_s,
+                              std::uintptr_t u_s1, std::uintptr_t buf, std::uintptr_t stream) {
+    W3D_REQUIRE(mode >= 0 && mode <= 2, "launch_box_copy: mode 0 (pack), 1 (unpack) or 2 (NaN fill)");
+    launch_box_copy(l, t, mode, dptr<double>(u_s), dptr<double>(u_s1), dptr<double>(buf), sptr(stream));
+  });
+  m.def("launch_field_hash", [](const Layout& l, std::uintptr_t f, std::uintptr_t out, std::uintptr_t stream) {
+    launch_field_hash(l, dptr<const double>(f), dptr<unsigned long long>(out), sptr(stream));
+  }, "adds the hash of the owned nodes of field f into the 64-bit word at `out` (zeroed by the caller)");
   m.def("gpu_error_blocks", &error_blocks);
   m.def("gpu_error", [](const Layout& l, std::uintptr_t u, const LBox& b, std::uintptr_t s, double ct,
                         std::uintptr_t partials, std::uintptr_t stream) {

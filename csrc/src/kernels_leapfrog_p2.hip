@@ -26,6 +26,7 @@
 // One pass is bit-identical to S single steps (stencil.hpp formulas and operation order), the analytic-start pass to
 // k_init_first + S steps. Tests: tests/test_gpu_kernels.py (test_leapfrog_p2_*).
 #include "wave3d/leapfrog_p2_launch.hpp"
+#include "wave3d/pass_grid.hpp"
 
 #ifdef W3D_EXPERIMENT_WGTIME
 #include <array>
@@ -45,45 +46,8 @@ struct P2Plan {
   int nblocks = 0;
 };
 
-// LDS budget of a pass: the largest x chunk whose sin table still fits next to the planes (the analytic start uses
-// the same planes: its φ values are table products)
-int p2_max_xlen(int S) {
-  const size_t cap = 160 * 1024 - 2 * 16 * sizeof(double) - 256;  // minus the reduction arrays (+ alignment slack)
-  size_t base = 0;
-  switch (S) {
-    case 2: base = p2_lds_bytes<2>(0); break;
-    case 3: base = p2_lds_bytes<3>(0); break;
-    case 4: base = p2_lds_bytes<4>(0); break;
-    default: base = p2_lds_bytes<5>(0); break;
-  }
-  if (base >= cap) return 0;
-  return static_cast<int>((cap - base) / sizeof(double)) - (2 * S + 4);
-}
-
-// workgroup grid of a pass over box b: the (y, z) tile grid times the x chunks; returns the launch's block count
-int p2_grid(const LBox& b, const LeapfrogTbTiling& t, int S, int* nty, int* ntz, int* xlen, int* nxc) {
-  *nty = static_cast<int>(ceil_div(b.y1 - b.y0, kT));
-  *ntz = static_cast<int>(ceil_div(b.z1 - b.z0, kT));
-  const int tiles = *nty * *ntz;
-  const i64 nxb = b.x1 - b.x0;
-  i64 want = 1;
-  // x chunks when the tile grid alone leaves CUs idle (at least min_chunk planes each), or when the x sin table of
-  // the whole range would not fit the LDS. (At most target_blocks workgroups: one CU each. Rounding the chunk count up
-  // instead put e.g. a 7 × 7-tile interior box on 294 workgroups — 256 and then a second round of 38.)
-  if (t.target_blocks > tiles) want = imin(imax(1, t.target_blocks / tiles), imax(1, nxb / imax(1, t.min_chunk)));
-  const int maxlen = p2_max_xlen(S);
-  W3D_REQUIRE(maxlen >= 1, "leapfrog_p2: the tile does not fit in LDS");
-  want = imax(want, ceil_div(nxb, maxlen));
-  *xlen = static_cast<int>(ceil_div(nxb, want));
-  *nxc = static_cast<int>(ceil_div(nxb, *xlen));
-  return tiles * *nxc;  // (unrounded: the launch grid rounds the sum of its boxes up to whole XCD shares)
-}
-
-int p2_round(int blocks, const LeapfrogTbTiling& t) { return t.xcd_remap ? static_cast<int>(round_up(blocks, 8)) : blocks; }
-
-// the checks a box must pass, and its grid (tiles × x chunks) as box k of a launch whose boxes before it take blk0
-// workgroups
-void p2_box(const Layout& l, const LBox& b, const LeapfrogTbTiling& t, const LBox& real, int blk0, P2Box& bx) {
+// the checks a box must pass; its grid (tiles × x chunks, first workgroup) is g (pass_grid.hpp p2_launch_grid)
+void p2_box(const Layout& l, const LBox& b, const LeapfrogTbTiling& t, const LBox& real, const PassBoxGrid& g, P2Box& bx) {
   const int S = t.stages;
   W3D_REQUIRE(leapfrog_p2_supported(l, b, S), "leapfrog_p2: the box must lie in the rank's y/z range on whole pairs");
   // x: u^{n+k} (k < S) is read up to S−k planes beyond the box (real there, or beyond the global boundary); u^n is
@@ -104,20 +68,21 @@ void p2_box(const Layout& l, const LBox& b, const LeapfrogTbTiling& t, const LBo
   bx.z0 = static_cast<int>(b.z0);
   bx.y1 = static_cast<int>(b.y1);
   bx.z1 = static_cast<int>(b.z1);
-  bx.blk0 = blk0;
+  bx.blk0 = g.blk0;
   // ghost-plane stores of u^{n+S−1}: only on a side at the rank's face, within the real (computed) range
   const LBox full = compute_box(l);
   bx.gxl = (t.ghost_x1 & 1) && b.x0 == full.x0 ? 1 : 0;
   bx.gxh = (t.ghost_x1 & 2) && b.x1 == full.x1 ? 1 : 0;
   W3D_REQUIRE(!bx.gxl || (real.x0 <= b.x0 - 1 && b.x0 - 1 >= -l.xg), "leapfrog_p2: ghost plane x0 − 1 not computed");
   W3D_REQUIRE(!bx.gxh || (real.x1 >= b.x1 + 1 && b.x1 < l.nx + l.xg), "leapfrog_p2: ghost plane x1 not computed");
-  bx.nty = bx.ntz = bx.nxc = 0;
-  bx.xlen = 1;
-  if (b.x1 > b.x0 && b.y1 > b.y0 && b.z1 > b.z0) p2_grid(b, t, S, &bx.nty, &bx.ntz, &bx.xlen, &bx.nxc);
+  bx.nty = g.nty;
+  bx.ntz = g.ntz;
+  bx.xlen = g.xlen;
+  bx.nxc = g.nxc;
 }
 
-// A launch over n boxes (n ≤ kP2Boxes): one grid, box k from workgroup blk0_k on. With several boxes each one's
-// x-chunk target is its share of t.target_blocks by work (tiles × planes), so together they fill the GPU once.
+// A launch over n boxes (n ≤ kP2Boxes): one grid, box k from workgroup blk0_k on; the block counts are the host-side
+// arithmetic of pass_grid.hpp (p2_launch_grid), which also sizes the partial slots.
 P2Plan make_plan_p2(const Layout& l, const LBox* boxes, int n, const LeapfrogTbTiling& t, LBox real, bool init) {
   const int S = t.stages;
   W3D_REQUIRE(S >= 2 && S <= 5, "leapfrog_p2: stages must be 2..5");
@@ -146,30 +111,15 @@ P2Plan make_plan_p2(const Layout& l, const LBox* boxes, int n, const LeapfrogTbT
   p.gx0 = static_cast<int>(l.gx0);
   p.gy0 = static_cast<int>(l.gy0);
   p.gz0 = static_cast<int>(l.gz0);
-  double work = 0.0;
-  for (int k = 0; k < n; ++k)
-    work += static_cast<double>(ceil_div(imax(0, boxes[k].y1 - boxes[k].y0), kT) *
-                                ceil_div(imax(0, boxes[k].z1 - boxes[k].z0), kT) * imax(0, boxes[k].x1 - boxes[k].x0));
-  int blk = 0;
+  const P2LaunchGrid gr = p2_launch_grid(boxes, n, t);
   p.nbox = n;
-  p.chunked = 0;
-  p.xlen_max = 1;
-  for (int k = 0; k < n; ++k) {
-    LeapfrogTbTiling tk = t;
-    if (n > 1 && work > 0.0) {
-      const double wk = static_cast<double>(ceil_div(imax(0, boxes[k].y1 - boxes[k].y0), kT) *
-                                            ceil_div(imax(0, boxes[k].z1 - boxes[k].z0), kT) *
-                                            imax(0, boxes[k].x1 - boxes[k].x0));
-      tk.target_blocks = imax(1, static_cast<int>(t.target_blocks * wk / work));
-    }
-    p2_box(l, boxes[k], tk, real, blk, p.box[k]);
-    blk += p.box[k].nty * p.box[k].ntz * p.box[k].nxc;
-    if (p.box[k].nxc > 1) p.chunked = 1;
-    p.xlen_max = imax(p.xlen_max, p.box[k].xlen);
-  }
+  p.chunked = gr.chunked ? 1 : 0;
+  p.xlen_max = gr.xlen_max;
+  for (int k = 0; k < n; ++k) p2_box(l, boxes[k], t, real, gr.box[k], p.box[k]);
+  const int blk = gr.nactive;
   p.nactive = blk;
   if (blk == 0) return pl;
-  pl.nblocks = p2_round(blk, t);
+  pl.nblocks = gr.nblocks;
   p.nblocks = pl.nblocks;
   p.xcd_remap = t.xcd_remap ? 1 : 0;
   p.xper = pl.nblocks / 8;
@@ -225,13 +175,8 @@ unsigned long long* wgtime_slot(int nblocks, int S, bool init) {
 }  // namespace
 
 int leapfrog_p2_partials(const Layout& l, const LBox& box, const LeapfrogTbTiling& t) {
-  // (the largest block count over S = 2..5: the chunk length shrinks with S, whose levels share the LDS with the
-  // chunk's x sin table — ADVICE r5: S = 2 alone undercounted boxes longer than the S = 5 chunk)
   (void)l;
-  if (box.x1 <= box.x0 || box.y1 <= box.y0 || box.z1 <= box.z0) return 0;
-  int n = 0, nty = 0, ntz = 0, xlen = 0, nxc = 0;
-  for (int S = 2; S <= 5; ++S) n = imax(n, p2_round(p2_grid(box, t, S, &nty, &ntz, &xlen, &nxc), t));
-  return n;
+  return p2_partials(box, t);
 }
 
 std::vector<int> leapfrog_p2_table(int stages, std::vector<long>* geometry) {

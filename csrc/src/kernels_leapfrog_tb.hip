@@ -76,13 +76,9 @@ size_t leapfrog_tb_lds_bytes(int stages) {
 }
 
 int leapfrog_tb_partials(const Layout& l, const LBox& box, const LeapfrogTbTiling& t) {
-  // the block count depends on the (y,z) tiling and the x chunks only: the widest real ranges pass the halo checks
-  const LBox real{-l.xg, l.nx + l.xg, -l.yg, l.ny + l.yg, -l.zg, l.nz + l.zg};
-  LeapfrogTbTiling t1 = t;
-  t1.stages = 2;  // (block count independent of S; S = 2 keeps the ghost-depth checks satisfiable)
-  const int n = make_plan_tb(l, box, t1, real).nblocks;
-  // (the pair-tiled pass may split x differently: a slot holds either kernel's partials)
-  return t.p2 && leapfrog_p2_supported(l, box, 2) ? std::max(n, leapfrog_p2_partials(l, box, t)) : n;
+  // (the block count depends on the (y,z) tiling and the x chunks only, and a slot holds either kernel's partials:
+  // pass_grid.hpp)
+  return tb_partials(l, box, t);
 }
 
 void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,

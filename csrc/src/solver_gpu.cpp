@@ -1,5 +1,6 @@
 // GPU solver runtime. See wave3d/solver.hpp.
 #include "wave3d/capture_guard.hpp"
+#include "wave3d/pass_grid.hpp"
 #include "wave3d/solver.hpp"
 
 #include <rccl/rccl.h>
@@ -266,13 +267,8 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
   if ((sch_.mode == Mode::kFusedSingle || sch_.mode == Mode::kDeepTb) && sch_.opt.tb && !sch_.full.empty()) {
     LeapfrogTbTiling t = sch_.opt.tiling_tb;
     t.stages = sch_.opt.temporal;  // partials per level do not depend on the stage count
-    n_tb_ = leapfrog_tb_partials(sch_.lay, sch_.full, t);
-    // multi-rank units also launch sub-boxes of the compute box (shells, interior), whose fewer tiles may be split into
-    // more x chunks: at most tiles · ceil(target / tiles) < tiles + target blocks (their slots are n_tb_ wide)
-    if (sch_.mode == Mode::kDeepTb)
-      n_tb_ = static_cast<int>(imax(n_tb_, round_up(ceil_div(sch_.full.y1 - sch_.full.y0, kTbTile) *
-                                                            ceil_div(sch_.full.z1 - sch_.full.z0, kTbTile) +
-                                                        t.target_blocks, 8)));
+    // (multi-rank units also launch sub-boxes of the compute box, shells and interior: pass_grid.hpp)
+    n_tb_ = tb_slot_blocks(sch_.lay, sch_.full, t, sch_.mode == Mode::kDeepTb);
     leapfrog_tb_prepare(sch_.push);
   }
   int n_deep = 0;
@@ -620,14 +616,11 @@ bool GpuSolver::tb_pass_boxes(const UnitPlan& u, const std::vector<LBox>& boxes,
   if (boxes.size() < 2 || boxes.size() > static_cast<size_t>(kP2MaxBoxes) || !sch_.opt.tiling_tb.p2 || sch_.push ||
       (pk_dev_ != nullptr && pk_host_[u.depth].w == u.depth) || (u.analytic && u.steps > 4))
     return false;
-  // (only where the shells' tiles alone do not fill the GPU: a 2048³ block rank's x-slab shell has 961 tiles of 5
-  // planes beside 63 border tiles of 1024 — one grid then runs no faster than three, and measured slower)
-  i64 tiles = 0;
-  for (const LBox& b : boxes) {
-    if (!leapfrog_p2_supported(sch_.lay, b, u.steps)) return false;
-    tiles += ceil_div(imax(0, b.y1 - b.y0), kTbTile) * ceil_div(imax(0, b.z1 - b.z0), kTbTile);
-  }
-  if (tiles > sch_.opt.tiling_tb.target_blocks) return false;
+  // (only where the shells' tiles alone do not fill the GPU and the combined grid fits the partial slot: pass_grid.hpp;
+  // otherwise one launch per box, each of which fits)
+  LeapfrogTbTiling ts = sch_.opt.tiling_tb;
+  ts.stages = u.steps;
+  if (tb_shells_launch_blocks(sch_.lay, boxes.data(), static_cast<int>(boxes.size()), ts, n_tb_) == 0) return false;
   TbArgs a = tb_args(u);
   // (no XCD remap: the boxes' workgroups differ in length, and a contiguous logical range per XCD put the long ones
   // on a few XCDs; dispatch order deals consecutive workgroups to the XCDs round-robin)

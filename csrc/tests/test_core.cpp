@@ -13,6 +13,7 @@
 
 #include "wave3d/cpu.hpp"
 #include "wave3d/decomp.hpp"
+#include "wave3d/pass_grid.hpp"
 #include "wave3d/problem.hpp"
 #include "wave3d/schedule.hpp"
 #include "wave3d/stencil.hpp"
@@ -484,6 +485,146 @@ void test_traffic() {
   }
 }
 
+// Workgroup counts of every LDS pass launch (pass_grid.hpp) against the partial slot the solver sizes once: an
+// over-wide grid — a launch asked for more workgroups than its slot holds — aborts the solve inside the graph capture
+// ("bad grid_blocks"). `over` counts the units whose combined shell launch, with only the parent's guard (Σ tiles ≤
+// target_blocks), would have exceeded the slot.
+void check_box_grid(const PassBoxGrid& g, const LBox& b, int maxlen) {
+  if (b.empty()) {
+    CHECK(g.blocks() == 0);
+    return;
+  }
+  const i64 nxb = b.x1 - b.x0;
+  CHECK(g.nty == ceil_div(b.y1 - b.y0, kTbTile) && g.ntz == ceil_div(b.z1 - b.z0, kTbTile));
+  CHECK(g.nxc >= 1 && g.xlen >= 1 && g.xlen <= maxlen);
+  CHECK(static_cast<i64>(g.xlen) * g.nxc >= nxb);        // the chunks cover the x range ...
+  CHECK(static_cast<i64>(g.xlen) * (g.nxc - 1) < nxb);   // ... and the last one is not empty
+}
+
+int check_unit_grids(const RankSchedule& s, const UnitPlan& u, int target) {
+  LeapfrogTbTiling t = s.opt.tiling_tb;
+  t.target_blocks = target;
+  LeapfrogTbTiling tmax = t;
+  tmax.stages = s.opt.temporal;
+  const int slot = tb_slot_blocks(s.lay, s.full, tmax, s.mode == Mode::kDeepTb);
+  CHECK(slot > 0 && (!t.xcd_remap || slot % 8 == 0));
+  t.stages = u.steps;
+  // one launch per box (GpuSolver::tb_pass): the pair-tiled kernel where it applies, else k_leapfrog_tb (S ≤ 4)
+  auto one = [&](const LBox& b) {
+    if (b.empty()) return;
+    if (t.p2 && leapfrog_p2_supported(s.lay, b, u.steps) && !(u.analytic && u.steps > 4)) {
+      const P2LaunchGrid g = p2_launch_grid(&b, 1, t);
+      check_box_grid(g.box[0], b, p2_max_xlen(u.steps));
+      CHECK(g.box[0].blk0 == 0 && g.nactive == g.box[0].blocks() && g.nblocks >= g.nactive);
+      CHECK(g.nblocks <= slot);
+    } else {
+      CHECK(u.steps <= 4);
+      const PassBoxGrid g = tb_box_grid(b, t);
+      check_box_grid(g, b, 1 << 30);
+      CHECK(tb_round(g.blocks(), t) <= slot);
+    }
+  };
+  one(u.interior);
+  for (const LBox& b : u.shells) one(b);
+  if (u.shells.size() < 2) return 0;
+  // all shells in one launch (GpuSolver::tb_pass_boxes): only where the combined grid fits the slot
+  const int n = static_cast<int>(u.shells.size());
+  const int used = tb_shells_launch_blocks(s.lay, u.shells.data(), n, t, slot);
+  CHECK(used <= slot);
+  if (n > kP2MaxBoxes) {
+    CHECK(used == 0);
+    return 0;
+  }
+  LeapfrogTbTiling tc = t;
+  tc.xcd_remap = false;
+  const P2LaunchGrid g = p2_launch_grid(u.shells.data(), n, tc);
+  int blk = 0;
+  i64 tiles = 0;
+  bool p2 = t.p2;
+  for (int k = 0; k < n; ++k) {
+    const LBox& b = u.shells[static_cast<size_t>(k)];
+    p2 = p2 && leapfrog_p2_supported(s.lay, b, u.steps);
+    check_box_grid(g.box[k], b, p2_max_xlen(u.steps));
+    CHECK(g.box[k].blk0 == blk);  // prefix sums
+    blk += g.box[k].blocks();
+    tiles += g.box[k].tiles();
+  }
+  CHECK(g.nactive == blk && g.nblocks == blk);
+  const bool parent_takes = p2 && tiles <= target;  // the guard before the slot check existed
+  CHECK(used == (parent_takes && g.nblocks <= slot ? g.nblocks : 0));
+  return parent_takes && g.nblocks > slot ? 1 : 0;
+}
+
+int sweep_pass_grids(i64 N, const char* decomp, int world, const std::vector<int>& ranks) {
+  int over = 0;
+  for (int temporal = 2; temporal <= 5; ++temporal)
+    for (int target : {12, 248, 256})
+      for (int r : ranks) {
+        SolverOptions o;
+        o.decomp = decomp;
+        o.temporal = temporal;
+        const RankSchedule s = sched(N, 20, o, r, world);
+        CHECK(world == 1 ? s.mode == Mode::kFusedSingle : s.mode == Mode::kDeepTb);
+        // a fresh solve, and one resumed at every level the pass splitter can be entered at: passes of every depth
+        // 2..temporal as units and as the depth of the exchange that follows
+        // (2-step passes cannot cover an odd number of remaining steps: plan_units refuses those starts)
+        std::vector<std::vector<UnitPlan>> plans;
+        for (int n0 = 1; n0 <= 7; ++n0) try {
+            plans.push_back(n0 == 1 ? fresh_units(s) : plan_units(s, n0, false));
+          } catch (const std::exception&) {
+          }
+        CHECK(plans.size() >= 3);
+        for (const std::vector<UnitPlan>& us : plans)
+          for (const UnitPlan& u : us)
+            if (u.fused()) over += check_unit_grids(s, u, target);
+      }
+  if (over > 0) std::printf("test_pass_grids: N = %lld %s: %d combined shell launches wider than their slot\n",
+                            static_cast<long long>(N), decomp, over);
+  return over;
+}
+
+void test_pass_grids() {
+  CHECK(p2_max_xlen(2) >= 512 && p2_max_xlen(5) >= 512 && p2_max_xlen(5) < p2_max_xlen(2));
+  // the hand calculation of an interior rank with 11 × 11 tiles (352² faces, 3×3×3 at N = 1056), S = 5, target 256:
+  // x slabs 81 + 81, y rows 66 + 66, z columns 54 + 54 = 402 workgroups against a slot of 384
+  {
+    SolverOptions o;
+    o.decomp = "3x3x3";
+    const RankSchedule s = sched(1056, 20, o, 13, 27);
+    CHECK(s.mode == Mode::kDeepTb && s.opt.temporal == 5 && s.lay.ny == 352 && s.lay.nz == 352);
+    std::vector<LBox> shells;
+    LBox interior;
+    deep_split(s.full, s.nb, 5, kTbTile, shells, interior);
+    CHECK(shells.size() == 6);
+    LeapfrogTbTiling t = s.opt.tiling_tb;
+    t.stages = 5;
+    t.target_blocks = 256;
+    const int slot = tb_slot_blocks(s.lay, s.full, t, true);
+    CHECK(slot == 384);
+    t.xcd_remap = false;
+    const P2LaunchGrid g = p2_launch_grid(shells.data(), 6, t);
+    int tiles = 0;
+    for (int k = 0; k < 6; ++k) tiles += g.box[k].tiles();
+    CHECK(tiles == 202 && tiles <= 256);  // the parent's only guard lets the launch through ...
+    CHECK(g.nblocks == 402);              // ... which needs more workgroups than the slot holds
+    CHECK(tb_shells_launch_blocks(s.lay, shells.data(), 6, t, slot) == 0);  // now: one launch per box
+  }
+  int over = 0;
+  CHECK(sweep_pass_grids(512, "slab", 1, {0}) == 0);
+  over += sweep_pass_grids(1056, "3x3x3", 27, {13, 0, 26, 4});
+  over += sweep_pass_grids(1152, "3x3x3", 27, {13, 0, 26});
+  over += sweep_pass_grids(1536, "4x4x4", 64, {21, 0, 63});
+  over += sweep_pass_grids(2048, "2x2x2", 8, {0, 7});
+  CHECK(sweep_pass_grids(512, "slab", 2, {0, 1}) == 0);
+  CHECK(sweep_pass_grids(512, "slab", 8, {0, 3, 7}) == 0);
+  // the small shapes of the GPU tests (tests/test_gpu_rank_pass.py)
+  over += sweep_pass_grids(100, "3x3x3", 27, {13});
+  over += sweep_pass_grids(67, "2x2x2", 8, {0, 7});
+  over += sweep_pass_grids(70, "1x2x3", 6, {4});
+  over += sweep_pass_grids(66, "slab", 3, {1});
+  CHECK(over > 0);  // (the sweep reaches the regime the slot check exists for)
+}
+
 }  // namespace
 
 int main() {
@@ -498,6 +639,7 @@ int main() {
   test_mode_table();
   test_deep_tb_worlds();
   test_traffic();
+  test_pass_grids();
   std::printf("test_core: %d checks, %d failed\n", g_checks, g_fail);
   return g_fail == 0 ? 0 : 1;
 }

@@ -165,6 +165,23 @@ struct UnitPlan {
 // The units of a solve that starts at level start_n (1, 2 or a resumed step); analytic: the first is an analytic start.
 std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic);
 
+// --poison-ghosts where the messages land in the field buffers themselves (every schedule but the 3-D block passes,
+// whose receive regions k_box_copy fills): what a unit's exchange NaN-fills. `rows` runs of `count` doubles, `pitch`
+// apart, from `off` in `field`.
+//   before_pass = false  the receive range of a message, before the exchange that must overwrite it;
+//   before_pass = true   the u^{n+S−1} ghost plane the unit's own passes store (ghost_bits; the nodes of the compute
+//                        box's y / z range on plane −1 / nx of out1: not the zero slot, the boundary nodes or the row
+//                        padding, which no pass writes), on the passes' stream before the unit's first launch — a pass
+//                        that stops storing the plane then shows in every solve, not only while the buffer is fresh.
+// Together, on a slab unit followed by a pass of w steps: ghost planes [−w, 0) / [nx, nx + w) of u^{n+S} (out2) and
+// [−(w − 1), 0) / [nx, nx + w − 1) of u^{n+S−1} (out1), with or without ghost_store.
+struct PoisonRange {
+  MsgField field;
+  i64 off, count, rows, pitch;
+  bool before_pass;
+};
+std::vector<PoisonRange> plan_poison(const RankSchedule& s, const UnitPlan& u);
+
 // Copy-engine transport: link k = one neighbour; slab ranks [lo, hi] (faces that exist), block ranks the peers of
 // deep[] in direction order.
 struct LinkPlan {

@@ -260,8 +260,9 @@ class GpuSolver {
   template <class F>
   void timed(int phase, hipStream_t st, F&& f);
   void collect_phases(RunResult& r);
-  // --poison-ghosts: NaN into the ghost regions u's exchange fills (uf: the buffers u's pass writes)
-  void poison(const UnitPlan& u, const int uf[2], hipStream_t st);
+  // --poison-ghosts: NaN into the ghost regions u's exchange fills (uf: the buffers u's pass writes); before_pass: into
+  // the ghost plane u's passes store themselves (UnitPlan::ghost_bits), issued by unit_shell before their launches
+  void poison(const UnitPlan& u, const int uf[2], hipStream_t st, bool before_pass = false);
   // push transport (slab deep-tb)
   double* stg_ = nullptr;       // [parity][field (0: u^{n+S−1}, 1: u^{n+S})][side (0: lo ghosts, 1: hi)][T planes]
   unsigned* flags_ = nullptr;   // uncached: [0] raised by the lower neighbour, [1] by the upper, [4] timeout, [8] done

@@ -287,6 +287,19 @@ std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analyt
   return units;
 }
 
+std::vector<PoisonRange> plan_poison(const RankSchedule& s, const UnitPlan& u) {
+  std::vector<PoisonRange> v;
+  if (s.block_tb) return v;
+  const Layout& l = s.lay;
+  for (const MsgPlan& m : u.msgs) v.push_back(PoisonRange{m.field, m.recv_off, m.count, 1, 0, false});
+  // the plane plan_msgs left out of the kOut1 message of that side
+  for (int side = 0; side < 2; ++side)
+    if ((u.ghost_bits >> side) & 1)
+      v.push_back(PoisonRange{MsgField::kOut1, l.off(side == 0 ? -1 : l.nx, s.full.y0, s.full.z0), s.full.z1 - s.full.z0,
+                              s.full.y1 - s.full.y0, l.pitch, true});
+  return v;
+}
+
 std::vector<LinkPlan> plan_links(const RankSchedule& s) {
   std::vector<LinkPlan> v;
   if (!s.block_tb) {

@@ -461,6 +461,9 @@ void GpuSolver::unit_shell(int i) {
     for (int b = 0; b < 4; ++b)
       if (b != cur_ && b != old_) uf_[k++] = b;
   }
+  // (s0: every pass of the unit follows it there — the shells on the side stream wait for ev_shell_, recorded below —
+  // and the previous unit's passes, which read that plane of the same buffer as a ghost, precede it)
+  if (sch_.opt.poison_ghosts && u.ghost_bits) poison(u, uf_, s0_, true);
   const int nc = u.n + u.steps;
   const bool chk = is_check_[static_cast<size_t>(nc)] != 0;
   if (sch_.mode == Mode::kDeep) {
@@ -742,14 +745,21 @@ void GpuSolver::enqueue_solve() {
 
 // Debug aid: fill the ghost regions that the next exchange must overwrite with NaN, so a halo that
 // is not delivered shows up in the error norms at once instead of silently reusing stale values.
-void GpuSolver::poison(const UnitPlan& u, const int uf[2], hipStream_t st) {
+// before_pass: the ghost plane the unit's own passes store instead (schedule.hpp plan_poison), filled before they run.
+void GpuSolver::poison(const UnitPlan& u, const int uf[2], hipStream_t st, bool before_pass) {
   if (sch_.block_tb) {  // the ghost regions themselves (the messages land in a staging buffer first)
-    launch_box_copy(sch_.lay, unpack_tab_[u.depth], 2, u_[uf[1]], u_[uf[0]], nullptr, st);
+    if (!before_pass) launch_box_copy(sch_.lay, unpack_tab_[u.depth], 2, u_[uf[1]], u_[uf[0]], nullptr, st);
     return;
   }
-  for (const MsgPlan& m : u.msgs)
-    W3D_HIP(hipMemsetAsync(msg_buf(m.field, false, uf) + m.recv_off, 0xFF, static_cast<size_t>(m.count) * sizeof(double),
-                           st));
+  for (const PoisonRange& p : plan_poison(sch_, u)) {
+    if (p.before_pass != before_pass) continue;
+    double* dst = msg_buf(p.field, false, uf) + p.off;
+    if (p.rows == 1)
+      W3D_HIP(hipMemsetAsync(dst, 0xFF, static_cast<size_t>(p.count) * sizeof(double), st));
+    else
+      W3D_HIP(hipMemset2DAsync(dst, static_cast<size_t>(p.pitch) * sizeof(double), 0xFF,
+                               static_cast<size_t>(p.count) * sizeof(double), static_cast<size_t>(p.rows), st));
+  }
 }
 
 void GpuSolver::collect_phases(RunResult& r) {

@@ -362,6 +362,48 @@ bool boxes_meet(const LBox& a, const LBox& b) {
   return imax(a.x0, b.x0) < imin(a.x1, b.x1) && imax(a.y0, b.y0) < imin(a.y1, b.y1) && imax(a.z0, b.z0) < imin(a.z1, b.z1);
 }
 
+// --poison-ghosts of a slab unit whose exchange a pass of w steps follows (plan_poison): the message receive ranges and
+// the self-stored plane together are exactly ghost planes [−w, 0) / [nx, nx + w) of u^{n+S} and [−(w − 1), 0) /
+// [nx, nx + w − 1) of u^{n+S−1} on the sides that have a neighbour, each plane once, none of them owned; the
+// self-stored plane is poisoned before the pass, over the compute box's y / z range, and keeps its zero slot.
+void check_poison(const RankSchedule& s, const UnitPlan& u, int w) {
+  const std::vector<PoisonRange> pr = plan_poison(s, u);
+  if (s.block_tb) {  // (k_box_copy fills the receive regions of the DeepPlan)
+    CHECK(pr.empty());
+    return;
+  }
+  const Layout& l = s.lay;
+  std::set<i64> got[2], want[2];  // ghost planes of out1 (u^{n+S−1}) / out2 (u^{n+S})
+  int self = 0;
+  for (const PoisonRange& p : pr) {
+    CHECK(p.field == MsgField::kOut1 || p.field == MsgField::kOut2);
+    const int f = p.field == MsgField::kOut2 ? 1 : 0;
+    CHECK(p.off >= 0 && p.count > 0 && p.rows >= 1);
+    const i64 x = p.off / l.plane - l.xg;
+    if (p.before_pass) {
+      const int side = x < 0 ? 0 : 1;
+      CHECK(f == 0 && x == (side == 0 ? -1 : l.nx) && ((u.ghost_bits >> side) & 1));
+      CHECK(p.off == l.off(x, s.full.y0, s.full.z0) && p.count == s.full.z1 - s.full.z0 &&
+            p.rows == s.full.y1 - s.full.y0 && p.pitch == l.pitch && p.count <= p.pitch);
+      CHECK(p.off + (p.rows - 1) * p.pitch + p.count <= l.plane_off(x) + l.zero_off());
+      CHECK(got[0].insert(x).second);
+      ++self;
+    } else {
+      CHECK(p.rows == 1 && p.off % l.plane == 0 && p.count % l.plane == 0);
+      for (i64 k = 0; k < p.count / l.plane; ++k) CHECK(got[f].insert(x + k).second);
+    }
+  }
+  CHECK(self == (u.ghost_bits & 1) + (u.ghost_bits >> 1));
+  for (int side = 0; side < 2; ++side) {
+    if (!s.nb[0][side]) continue;
+    for (i64 d = 1; d <= w; ++d) want[1].insert(side == 0 ? -d : l.nx - 1 + d);
+    for (i64 d = 1; d <= w - 1; ++d) want[0].insert(side == 0 ? -d : l.nx - 1 + d);
+  }
+  CHECK(got[0] == want[0] && got[1] == want[1]);
+  for (int f = 0; f < 2; ++f)
+    for (i64 x : got[f]) CHECK((x < 0 || x >= l.nx) && x >= -l.xg && x < l.nx + l.xg);
+}
+
 // Every deep-tb world of the matrix: both ends of every message agree, message sizes are the region sizes, and the
 // overlapped units' shell boxes and interior tile the compute box on boxes the pair-tiled pass accepts.
 void test_deep_tb_worlds() {
@@ -452,9 +494,26 @@ void test_deep_tb_worlds() {
                       (m.recv_off + m.count <= s.lay.plane_off(0) || m.recv_off >= s.lay.plane_off(s.lay.nx)));
               }
             }
+            check_poison(s, u, w);
           }
         }
       }
+  // two-step deep halos: 2 ghost planes of u^{n+2}, 1 of u^{n+1}, all by message
+  SolverOptions o;
+  o.tb = false;
+  o.deep_min_planes = 3;
+  for (int r = 0; r < 3; ++r) {
+    const RankSchedule s = sched(66, 20, o, r, 3);
+    CHECK(s.mode == Mode::kDeep);
+    int nx = 0;
+    for (const UnitPlan& u : fresh_units(s))
+      if (u.exchange) {
+        CHECK(u.ghost_bits == 0);
+        check_poison(s, u, 2);
+        ++nx;
+      }
+    CHECK(nx == 8);
+  }
 }
 
 void test_traffic() {

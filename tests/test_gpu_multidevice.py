@@ -178,6 +178,36 @@ def test_multidevice_group_bitexact(gpu):
                 assert torch.equal(g.global_field(0), f0)
 
 
+@needs2
+@pytest.mark.parametrize("copy_engines", [False, True])
+def test_multidevice_group_random_state(gpu, copy_engines):
+    """Two slab ranks on two devices from the random loaded state of test_gpu_random_state.py (no mirror or axis
+    symmetry that could hide a lo/hi mix-up), RCCL and copy engines between the devices, two solves: the error log and
+    both final fields against the undecomposed CPU steps."""
+    import math
+
+    import test_gpu_random_state as rs
+    import torch
+
+    from mpi_cuda_amd.solver import Solver
+
+    _limit(MIN_S)
+    N = 66
+    G = rs._global(N)
+    g = Solver(rs._spec(N), backend="hip", transport="multi-device", world=2, rank=0, decomp="slab",
+               copy_engines=copy_engines, poison_ghosts=True)
+    g.set_state(G["prev"], G["cur"], rs.N0)
+    steps = list(range(rs.N0 + 1, rs.K + 1))
+    for _ in range(2):
+        r = g.run()
+        assert r.finite and r.steps == steps
+        assert r.max_err == [G["err"][n][0] for n in steps]
+        for n, e in zip(steps, r.rms_err):
+            assert math.isclose(e, G["err"][n][1], rel_tol=1e-12)
+        assert torch.equal(g.global_field(0), G["level"][rs.K])
+        assert torch.equal(g.global_field(1), G["level"][rs.K - 1])
+
+
 def test_multidevice_group_one_gpu(gpu):
     """The multi-device group's plumbing on whatever is visible (one GPU: ncclCommInitAll over one device, one
     thread): the path runs everywhere, not only on a node."""

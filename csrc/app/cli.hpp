@@ -62,6 +62,8 @@ struct Args {
   int target_blocks = 0;
   int nt_store = -1;
   std::string json, dump, trace, checkpoint, resume;
+  std::string initial;  // --initial PREFIX: solve from PREFIX.phi (u(.,0)) and, if present, PREFIX.psi (u_t(.,0))
+  bool energy = false;  // --energy: print the discrete energy at steps 1/2 and K-1/2 and its drift
   bool quiet = false;
   std::string program = "wave3d";  // reference program personality (argv[0])
 };
@@ -87,6 +89,9 @@ std::string jnum(double v);
 // empty for a cube, whose lines stay what they were
 std::string box_banner(const Problem& p);
 std::string box_json(const Problem& p);
+// --energy: the line printed after the error log, and the two keys it adds to --json
+void print_energy(double e_start, double e_end);
+std::string energy_json(double e_start, double e_end);
 std::string steps_json(const std::vector<int>& st, const std::vector<double>& mx, const std::vector<double>& rms);
 // solver options from the command line
 SolverOptions options_from(const Args& a, bool fake);

@@ -3,6 +3,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -102,6 +103,10 @@ constexpr Personality kPersonalities[] = {
                "  --dump PREFIX      write u^K: PREFIX[.rankR].bin (fp64, C order, owned nodes) + .json\n"
                "  --checkpoint P     write u^{K-1}, u^K as P.prev / P.cur dumps (resumable)\n"
                "  --resume P         start from the P.prev / P.cur checkpoint (step n0) and continue to K\n"
+               "  --initial P        solve from your own initial data: u(.,0) from the dump P.phi and, if present, u_t(.,0)\n"
+               "                     from P.psi (wave3d-dump-v1, global fields; face values ignored). The error lines then\n"
+               "                     are the difference from the eigenmode: use --energy\n"
+               "  --energy           print the discrete energy E(1/2), E(K-1/2) and its drift (with --initial; one rank)\n"
                "  --force            run even if the CFL condition is violated\n"
                "  --quiet            only the summary\n");
   std::exit(2);
@@ -188,6 +193,8 @@ Args parse(int argc, char** argv) {
     else if (s == "--dump") a.dump = next();
     else if (s == "--checkpoint") a.checkpoint = next();
     else if (s == "--resume") a.resume = next();
+    else if (s == "--initial") a.initial = next();
+    else if (s == "--energy") a.energy = true;
     else if (s == "--box") {
       const std::string v = next();  // LX,LY,LZ
       double e[3] = {0.0, 0.0, 0.0};
@@ -237,6 +244,8 @@ Args parse(int argc, char** argv) {
     a.prob.Ly = a.box[1];
     a.prob.Lz = a.box[2];
   }
+  if (!a.initial.empty() && !a.resume.empty()) usage("--initial and --resume exclude each other");
+  if (a.energy && a.initial.empty()) usage("--energy needs --initial (E(1/2) is kept by solves that start from it)");
   if (a.repeat < 1) a.repeat = 1;
   return a;
 }
@@ -271,6 +280,13 @@ std::string box_banner(const Problem& p) {
 std::string box_json(const Problem& p) {
   if (!p.is_box()) return "";
   return ", \"box\": [" + jexact(p.L) + ", " + jexact(p.edge_y()) + ", " + jexact(p.edge_z()) + "]";
+}
+void print_energy(double e_start, double e_end) {
+  std::printf("Energy: E(1/2) = %.15e, E(K-1/2) = %.15e, drift = %.3e\n", e_start, e_end,
+              std::fabs(e_end - e_start) / e_start);
+}
+std::string energy_json(double e_start, double e_end) {
+  return ", \"energy_start\": " + jexact(e_start) + ", \"energy_end\": " + jexact(e_end);
 }
 std::string steps_json(const std::vector<int>& st, const std::vector<double>& mx, const std::vector<double>& rms) {
   std::string o = "[";

@@ -18,6 +18,11 @@ int run_cpu(const Args& a) {
     const int n0 = load_checkpoint(a.resume, a.prob, prev, cur);
     s.set_state(prev.data(), cur.data(), n0);
   }
+  if (!a.initial.empty()) {
+    std::vector<double> phi, psi;
+    load_initial(a.initial, a.prob, phi, psi);
+    s.set_initial(phi.data(), psi.empty() ? nullptr : psi.data());
+  }
   if (a.serve) {  // (the rank-process protocol on the CPU solver: run / dump / quit — cli.hpp serve_loop)
     const std::string greeting = "{\"ready\": true, \"backend\": \"cpu\", \"rank\": 0, \"world\": 1, \"dims\": [1, 1, 1], "
                                  "\"schedule\": \"cpu-openmp\", \"mode\": \"cpu\", \"transport\": \"none\"}";
@@ -54,6 +59,8 @@ int run_cpu(const Args& a) {
     bench_s = wall_s() - t0;
   }
   if (!a.quiet) print_errors(r.steps, r.max_err, r.rms_err, a.prob.tau);
+  const double e_start = a.energy ? s.energy(1) : 0.0, e_end = a.energy ? s.energy(0) : 0.0;
+  if (a.energy) print_energy(e_start, e_end);
   const double gcell = a.prob.cell_updates() / best / 1e9;
   std::printf("Total time: %.6f s (init %.6f s, compute %.6f s), threads %d, %.3f GCell/s\n", best, rb.init_s,
               rb.compute_s, cpu_max_threads(), gcell);
@@ -71,6 +78,7 @@ int run_cpu(const Args& a) {
       << ", \"boundary\": " << jnum(rb.boundary_s) << ", \"exchange\": " << jnum(rb.exchange_s) << "}"
       << ", \"phases_slowest_rank_s\": {\"init\": " << jnum(rb.init_s) << ", \"compute\": " << jnum(rb.compute_s)
       << ", \"boundary\": " << jnum(rb.boundary_s) << ", \"exchange\": " << jnum(rb.exchange_s) << "}"
+      << (a.energy ? energy_json(e_start, e_end) : std::string())
       << ", \"steps\": " << steps_json(r.steps, r.max_err, r.rms_err) << "}\n";
   }
   if (!a.dump.empty()) write_dump(a.dump, a.prob, s.layout(), s.field(0), 0, 1, Dims{1, 1, 1});
@@ -82,6 +90,7 @@ int run_cpu(const Args& a) {
 // One rank of the multi-process CPU path (--cpu --np P): the reference's MPI / MPI+OpenMP programs.
 int run_cpu_rank(const Args& a, ShmGroup& g, int rank) {
   W3D_REQUIRE(a.resume.empty(), "--resume runs on one CPU process (--cpu) or on the GPU path, not the CPU ranks");
+  W3D_REQUIRE(a.initial.empty(), "--initial runs on one CPU process (--cpu) or on the GPU path, not the CPU ranks");
   try {
     CpuRankSolver s(a.prob, g, rank, a.check_every, a.threads);
     // fault injection: W3D_FAULT_RANK=r makes rank r fail before its first exchange

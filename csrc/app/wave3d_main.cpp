@@ -110,11 +110,17 @@ int serve(const Args& a, GpuSolver& s, const HostColl& hc, bool file_coll, const
 }
 
 int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop) {
+  W3D_REQUIRE(!a.energy, "energy: one rank only (multi-rank: Solver.energy assembles the global fields)");
   GpuGroup g(a.prob, o, a.group, a.group_transport);
   if (!a.resume.empty()) {
     std::vector<double> prev, cur;
     const int n0 = load_checkpoint(a.resume, a.prob, prev, cur);
     g.set_state(prev.data(), cur.data(), n0);
+  }
+  if (!a.initial.empty()) {
+    std::vector<double> phi, psi;
+    load_initial(a.initial, a.prob, phi, psi);
+    g.set_initial(phi.data(), psi.empty() ? nullptr : psi.data());
   }
   if (a.serve) {
     // --group P --serve: all P ranks in this process (the Python Solver(world=P, runtime="process") of ONE Python
@@ -269,6 +275,13 @@ int run_gpu(const Args& a) {
     const int n0 = load_checkpoint(a.resume, a.prob, prev, cur);
     s->set_state(prev.data(), cur.data(), n0);
   }
+  W3D_REQUIRE(!a.energy || (world == 1 && !fake),
+              "energy: one rank only (multi-rank: Solver.energy assembles the global fields)");
+  if (!a.initial.empty()) {
+    std::vector<double> phi, psi;
+    load_initial(a.initial, a.prob, phi, psi);
+    s->set_initial(phi.data(), psi.empty() ? nullptr : psi.data());
+  }
   if (a.serve) {
     const int rc = serve(a, *s, hc, file_coll, sched);
     if ((s->push() || s->sdma()) && !comm && !fake)
@@ -336,6 +349,8 @@ int run_gpu(const Args& a) {
              " produced a different error log than the warmup solve");
     r = rs.back();
   }
+  // --energy: of the last solve above, like --dump
+  const double e_start = a.energy ? s->energy(1) : 0.0, e_end = a.energy ? s->energy(0) : 0.0;
   // --dump: u^K of the last solve above (before the traced solve below overwrites the fields with its own)
   if (!a.dump.empty()) write_dump(a.dump, a.prob, s->layout(), s->download(0), rank, world, s->dims());
   // per-phase breakdown of the schedule that was timed: one more solve with the same kernels, traced with events
@@ -372,6 +387,7 @@ int run_gpu(const Args& a) {
                   d.px, d.py, d.pz, prop.gcnArchName, a.prob.courant());
       print_errors(r.steps, r.max_err, r.rms_err, a.prob.tau);
     }
+    if (a.energy) print_energy(e_start, e_end);
     const double gcell = a.prob.cell_updates() / best / 1e9;
     std::printf("Total time: %.6f s (solve region, max over %d rank%s; best of %d, mean %.6f s, first %.6f s)\n", best,
                 world, world > 1 ? "s" : "", a.repeat, mean, first);
@@ -427,6 +443,7 @@ int run_gpu(const Args& a) {
           << jnum(pp.interior_ms + pp.shell_ms) << ", \"shell\": " << jnum(pp.shell_ms) << ", \"exchange\": "
           << jnum(pp.comm_ms) << ", \"check\": " << jnum(pp.check_ms) << ", \"gather\": " << jnum(pp.gather_ms)
           << "}";
+      if (a.energy) j << energy_json(e_start, e_end);
       j << ", \"solve_times_s\": [";
       for (size_t i = 0; i < times.size(); ++i) j << (i ? ", " : "") << jnum(times[i]);
       j << "], \"steps\": [";

@@ -101,6 +101,15 @@ inline void deep_split(const LBox& full, const bool nb[3][2], i64 w, i64 T, std:
 // of any depth filled from the global field, the first pass after a resume needs no halo exchange.
 void global_to_local(const Layout& l, const double* global, double* local);
 
+// User-supplied initial data (set_initial): the layout φ / ψ are sliced into — the rank's box with one ghost layer more
+// than the solve layout on every axis, so the first step can be evaluated on every ghost node of the solve layout —
+// and the slicing itself: global_to_local, then exact zeros on the six global faces (their values are ignored).
+inline Layout initial_layout(const Problem& p, const Layout& solve) {
+  const Box b{solve.gx0, solve.gx0 + solve.nx, solve.gy0, solve.gy0 + solve.ny, solve.gz0, solve.gz0 + solve.nz};
+  return make_layout(p, b, 16, solve.xg + 1, solve.yg + 1, solve.zg + 1);
+}
+void initial_to_local(const Layout& src, const double* global, double* local);
+
 
 // Error accumulator: L∞ and Σe² over the updated (interior) nodes.
 struct ErrAcc {
@@ -115,6 +124,30 @@ int cpu_max_threads();
 // u0 = φ and u1 = u0 + τ²/2 Δ_h u0 over the whole local allocation, ghosts included (they are analytic, so no halo
 // exchange is needed before the first leapfrog step). `s` = &sin_table_ext[1].
 void cpu_init_first(const Layout& l, const Coeffs& c, const double* s, double* u0, double* u1);
+
+// First step from stored initial data: u0 = φ and u1 = φ + τψ + (τ²/2)Δ_h φ (stencil.hpp first_step, first_step_psi;
+// psi = nullptr: ψ = 0, its term skipped) over the whole allocation of the solve layout `l`, ghosts included; zeros on
+// and outside the global boundary and in the padding. phi / psi: local arrays in `src` = initial_layout(...), filled
+// by initial_to_local. With ψ absent and φ the eigenmode array, u1 equals cpu_init_first's bit for bit.
+void cpu_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
+                          const double* psi, double* u0, double* u1);
+
+// Discrete energy of two stored levels a = u^n, b = u^{n+1} (leapfrog conserves it exactly in exact arithmetic):
+//   E^{n+1/2} = V/2 · [ Σ ((b − a)/τ)² + Σ_d (1/h_d²) Σ_{edges (p,q) along d} (b_p − b_q)(a_p − a_q) ],  V = hx·hy·hz,
+// every grid edge counted once, by its lower endpoint, over the owned nodes of `l` (boundary nodes hold 0). Per node:
+// kinetic ((b − a)·(1/τ))², potential ((b_x+ − b)(a_x+ − a))·ihx2 + ((b_y+ − b)(a_y+ − a))·ihy2 + ((b_z+ − b)(a_z+ − a))·ihz2
+// — k_energy evaluates the same expressions, so the two differ by their summation order alone. Plain fixed loop order:
+// one accumulator per z row, the rows of a plane added in y order, the planes in x order (the same bits for every
+// thread count); depth = the additions on the longest path, nz + ny + nx.
+struct EnergySums {
+  double kin = 0.0, pot = 0.0;  // Σ kinetic terms, Σ potential terms (unscaled)
+  double abs = 0.0;             // Σ |kinetic term| + Σ |each edge product|: the scale of the summation error
+  i64 depth = 0;
+};
+EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double* a, const double* b);
+inline double energy_value(const Problem& p, double kin, double pot) {
+  return (0.5 * ((p.hx() * p.hy()) * p.hz())) * (kin + pot);
+}
 
 // u^{n+1} = 2u^n − u^{n−1} + τ²Δ_h u^n on `box`, written in place over u^{n−1} (`old_out`).
 // If acc != nullptr also accumulates the error vs the analytic solution φ·ct over the box.
@@ -157,6 +190,14 @@ class CpuSolver {
   // Start every following run() at step n0 from u^{n0−1} = prev and u^{n0} = cur (global (N+1)³ fields) instead of
   // the analytic initial condition: the leapfrog continues to K and checks the steps after n0.
   void set_state(const double* prev_global, const double* cur_global, int n0);
+  // Start every following run() from user-supplied initial data φ = u(·,0), ψ = u_t(·,0) (global (N+1)³ fields, face
+  // values ignored; psi_global = nullptr: ψ = 0): u⁰, u¹ by cpu_first_step_field, then the ordinary steps from n = 1.
+  // The error columns then are the difference from the eigenmode. It and set_state replace each other.
+  void set_initial(const double* phi_global, const double* psi_global);
+  // E^{K−1/2} of the last run()'s u^{K−1}, u^K (which = 0), or E^{1/2} of its u⁰, u¹ (which = 1; after set_initial)
+  double energy(int which) const;
+  // the sums behind energy(which): kin, pot, abs (the error scale) and the summation depth
+  EnergySums energy_sums(int which) const;
   // u^K (which = 0) or u^{K-1} (which = 1), padded local layout (single rank = whole domain).
   const std::vector<double>& field(int which) const { return which == 0 ? u_[final_] : u_[1 - final_]; }
   const Layout& layout() const { return lay_; }
@@ -171,6 +212,11 @@ class CpuSolver {
   int final_ = 1;
   int resume_n_ = 0;                     // > 0: start step of a resumed run
   std::vector<double> resume_[2];        // local u^{n0−1}, u^{n0}
+  bool initial_ = false;                 // set_initial: runs start from init_[0] = φ, init_[1] = ψ (empty: none)
+  Layout init_lay_;
+  std::vector<double> init_[2];
+  EnergySums e_start_;                   // of u⁰, u¹ of the last run() after set_initial
+  int runs_ = 0;
 };
 
 }  // namespace wave3d

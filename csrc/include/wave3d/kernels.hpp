@@ -37,6 +37,24 @@ int init_two_partials(const Layout& l);
 void launch_init_two(const Layout& l, const Coeffs& c, const double* d_s, double* u1, double* u2, double ct2,
                      Partial* partials, hipStream_t stream);
 
+// First step from stored initial data (kernels_initial.hip): u⁰ = φ, u¹ = φ + τψ + (τ²/2)Δ_h φ (stencil.hpp
+// first_step / first_step_psi; psi = nullptr: ψ = 0, the term is skipped) over the WHOLE solve layout `l` — owned and
+// ghost nodes, exact zeros on and outside the global boundary, in the padding and the zero slot. phi / psi are device
+// buffers in `src` = make_layout(prob, box, 16, l.xg + 1, l.yg + 1, l.zg + 1) filled by initial_to_local (cpu.hpp).
+void launch_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
+                             const double* psi, double* u0, double* u1, hipStream_t stream);
+
+// Discrete energy of two stored levels a = u^n, b = u^{n+1} over the owned nodes of `l` (cpu.hpp cpu_energy has the
+// formula; edges to the upper neighbours read the ghost layer, so the fields must be valid there: one rank, or fresh
+// ghosts). launch_energy writes energy_partials(l) partials (x: kinetic sum, y: potential sum), launch_energy_reduce
+// adds them in a fixed order into out[0]; E = energy_value(problem, out[0].x, out[0].y). energy_depth(l): the depth D
+// of that reduction tree (kernels_initial.hip, k_energy's header).
+int energy_partials(const Layout& l);
+int energy_depth(const Layout& l);
+void launch_energy(const Layout& l, const Coeffs& c, double tau, const double* a, const double* b, Partial* partials,
+                   hipStream_t stream);
+void launch_energy_reduce(const Partial* partials, int n, Partial* out, hipStream_t stream);
+
 // Runs one leapfrog step over up to 6 boxes in a single launch. If `partials` is non-null the error vs φ·ct is reduced
 // per workgroup into partials[0 .. leapfrog_blocks()).
 void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox* boxes, int nbox,

@@ -64,7 +64,12 @@ void write_checkpoint(const std::string& prefix, const Problem& p, const Layout&
 // numbers after "key": in a one-line JSON object (the sidecars above)
 std::vector<double> json_numbers(const std::string& text, const std::string& key);
 // the GLOBAL (N+1)³ field of a dump of any decomposition; checks N, tau and L against `p`; returns its step
-int load_dump_global(const std::string& prefix, const Problem& p, std::vector<double>& g);
+// (`what`: the option named in the refusals, "resume: dump N differs ...")
+int load_dump_global(const std::string& prefix, const Problem& p, std::vector<double>& g,
+                     const std::string& what = "resume");
+// PREFIX.phi → φ = u(·,0) and, when it exists, PREFIX.psi → ψ = u_t(·,0) (else psi is left empty): the same format and
+// the same N / tau / L / box checks as a checkpoint's dumps (refusals start with "initial:")
+void load_initial(const std::string& prefix, const Problem& p, std::vector<double>& phi, std::vector<double>& psi);
 // PREFIX.prev / PREFIX.cur → u^{n0−1}, u^{n0}; returns n0
 int load_checkpoint(const std::string& prefix, const Problem& p, std::vector<double>& prev, std::vector<double>& cur);
 

@@ -110,6 +110,19 @@ class GpuSolver {
   // first pass needs no exchange) and continues the same schedule kinds to K, checking the steps after n0. The
   // state is uploaded at the start of each run (eager launches, no graph).
   void set_state(const double* prev_global, const double* cur_global, int n0);
+  // User-supplied initial data φ = u(·,0), ψ = u_t(·,0) (GLOBAL (N+1)³ C-order fields, face values ignored; psi_global
+  // = nullptr: ψ = 0). Each rank slices them ONCE into device-resident buffers with one ghost layer more than the solve
+  // layout; every following run() starts with k_first_step_field (u⁰, u¹ over every owned and ghost node, so the first
+  // pass needs no exchange) and runs the ordinary schedule from step 1 — no analytic start, no init2, nothing on the
+  // host per solve: the solve is graph-captured and run_batch pipelined exactly where the default solve is. The error
+  // log then is the difference from the eigenmode. set_state's preconditions for a start at step 1, with its messages.
+  // It and set_state replace each other; either drops the captured graph.
+  void set_initial(const double* phi_global, const double* psi_global);
+  // Discrete energy (cpu.hpp cpu_energy): which = 0: E^{K−1/2} of the retained u^{K−1}, u^K; which = 1: E^{1/2},
+  // computed inside the solve right after the first-step kernel (solves started by set_initial) and kept on the
+  // device. One rank only. energy_sums: the kinetic and potential sums themselves.
+  double energy(int which) const;
+  Partial energy_sums(int which) const;
 
   // Host copy of the local array holding u^K (which = 0) or u^{K−1} (which = 1), full padded layout.
   std::vector<double> download(int which) const;
@@ -244,6 +257,13 @@ class GpuSolver {
   std::vector<char> is_check_;
   int resume_n_ = 0;                  // > 0: runs start at this step from resume_[0..1]
   std::vector<double> resume_[2];     // local (padded) u^{n0−1}, u^{n0}
+  int initial_runs_ = 0;              // solves since set_initial (energy() refuses the fields of an older start)
+  bool initial_ = false;              // set_initial: runs start with k_first_step_field on init_[0] = φ, init_[1] = ψ
+  Layout init_lay_;                   // ... their layout (the solve layout's box, one ghost layer more)
+  double* init_[2] = {nullptr, nullptr};  // device (init_[1] null: ψ = 0)
+  mutable Partial* energy_part_ = nullptr;  // k_energy's partials, then [n] = E^{K−1/2}'s sums, [n + 1] = E^{1/2}'s
+  void energy_alloc() const;
+  void drop_graphs();
   hipGraphExec_t graph_exec_ = nullptr;
   int runs_ = 0;  // completed run() calls (RCCL ranks capture the graph only after one eager solve)
   int final_buf_ = 0;            // buffer index holding u^K after a solve
@@ -376,6 +396,7 @@ class GpuGroup {
   // RCCL communicators in use and the rank count each reports (rccl-self: world one-rank communicators)
   std::vector<int> comm_counts() const;
   void set_state(const double* prev_global, const double* cur_global, int n0);  // every rank (GpuSolver::set_state)
+  void set_initial(const double* phi_global, const double* psi_global);         // every rank (GpuSolver::set_initial)
 
  private:
   void enqueue();
@@ -383,6 +404,7 @@ class GpuGroup {
   std::vector<std::unique_ptr<GpuSolver>> ranks_;
   std::string transport_;
   bool graph_ = false;
+  bool graph0_ = false;  // graph_ as the constructor decided it (set_initial after a set_state restores it)
   int runs_ = 0;
   hipStream_t gs_ = nullptr;
   hipEvent_t fork_ = nullptr;

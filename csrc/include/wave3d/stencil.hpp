@@ -76,6 +76,18 @@ W3D_HD double first_step(double c, double s, double half_lam) {
 #endif
 }
 
+// First step from user-supplied initial data φ = u(·,0), ψ = u_t(·,0) (set_initial): u¹ = φ + τψ + (τ²/2)Δ_h φ, evaluated
+// as fma(τ, ψ, first_step(φ, s, half_lam)) — the ψ = 0 value first, exactly as above, then the τψ term added by ONE fma
+// applied last. Without ψ the fma is skipped entirely (not fed a zero): u¹ then is first_step's value bit for bit, so
+// the eigenmode array given as φ reproduces init_first's u¹.
+W3D_HD double first_step_psi(double u1, double psi, double tau) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fma(tau, psi, u1);
+#else
+  return std::fma(tau, psi, u1);
+#endif
+}
+
 // IEEE fused multiply-add on the host (bindings: the numpy emulators' rounding primitive)
 inline double fma_exact(double a, double b, double c) { return std::fma(a, b, c); }
 

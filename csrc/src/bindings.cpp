@@ -283,6 +283,48 @@ PYBIND11_MODULE(_C, m) {
     py::gil_scoped_release nogil;
     cpu_init_first(l, c, sp, a, b);
   });
+  m.def("initial_layout", &initial_layout, py::arg("problem"), py::arg("layout"),
+        "the layout set_initial slices phi / psi into: the solve layout's box with one ghost layer more per axis");
+  m.def("initial_to_local", [](const Layout& src, const darr& g) {
+    const i64 n = src.N + 1;
+    const double* gp = ro_ptr(g, n * n * n, "global");
+    darr out(static_cast<py::ssize_t>(src.total));
+    initial_to_local(src, gp, out.mutable_data());
+    return out;
+  }, py::arg("layout"), py::arg("field"), "a GLOBAL (N+1)^3 field sliced into `layout`, the six global faces zeroed");
+  m.def("cpu_first_step_field",
+        [](const Layout& l, const Layout& src, const Coeffs& c, double tau, const darr& phi, py::object psi, darr u0,
+           darr u1) {
+          const double* fp = ro_ptr(phi, src.total, "phi");
+          const double* sp = nullptr;
+          darr psi_a;
+          if (!psi.is_none()) {
+            psi_a = psi.cast<darr>();
+            sp = ro_ptr(psi_a, src.total, "psi");
+          }
+          double* a = mut_ptr(u0, l.total, "u0");
+          double* b = mut_ptr(u1, l.total, "u1");
+          py::gil_scoped_release nogil;
+          cpu_first_step_field(l, src, c, tau, fp, sp, a, b);
+        },
+        py::arg("layout"), py::arg("src"), py::arg("coeffs"), py::arg("tau"), py::arg("phi"), py::arg("psi"),
+        py::arg("u0"), py::arg("u1"));
+  m.def("cpu_energy",
+        [](const Problem& p, const Layout& l, const darr& a, const darr& b) {
+          const EnergySums e = cpu_energy(l, Coeffs::from(p), p.tau, ro_ptr(a, l.total, "a"), ro_ptr(b, l.total, "b"));
+          const double half_v = 0.5 * ((p.hx() * p.hy()) * p.hz());
+          py::dict d;
+          d["E"] = energy_value(p, e.kin, e.pot);
+          d["kin"] = e.kin;
+          d["pot"] = e.pot;
+          d["abs_terms"] = half_v * e.abs;
+          d["depth"] = e.depth;
+          return d;
+        },
+        py::arg("problem"), py::arg("layout"), py::arg("a"), py::arg("b"),
+        "discrete energy of a = u^n, b = u^{n+1} (local arrays in `layout`): E, its kinetic / potential sums, "
+        "abs_terms = V/2 * sum |terms| (the scale of the summation error) and the summation depth");
+  m.def("energy_value", &energy_value);
   m.def(
       "cpu_leapfrog",
       [](const Layout& l, const Coeffs& c, const darr& cur, darr old, const LBox& box, const darr& s, double ct,
@@ -342,7 +384,14 @@ PYBIND11_MODULE(_C, m) {
       .def("set_state", [](CpuSolver& s, const darr& prev, const darr& cur, int n0) {
         const i64 n = s.layout().N + 1;
         s.set_state(ro_ptr(prev, n * n * n, "prev"), ro_ptr(cur, n * n * n, "cur"), n0);
-      }, py::arg("prev"), py::arg("cur"), py::arg("step"));
+      }, py::arg("prev"), py::arg("cur"), py::arg("step"))
+      .def("set_initial", [](CpuSolver& s, const darr& phi, py::object psi) {
+        const i64 n = s.layout().N + 1;
+        darr psi_a;
+        if (!psi.is_none()) psi_a = psi.cast<darr>();
+        s.set_initial(ro_ptr(phi, n * n * n, "phi"), psi.is_none() ? nullptr : ro_ptr(psi_a, n * n * n, "psi"));
+      }, py::arg("phi"), py::arg("psi") = py::none())
+      .def("energy", &CpuSolver::energy, py::arg("which") = 0);
 
   // ---------------- GPU ----------------
   m.def("gpu_device_count", []() {
@@ -389,6 +438,16 @@ PYBIND11_MODULE(_C, m) {
                              std::uintptr_t stream) {
     launch_init_first(l, c, dptr<const double>(s) + 1, dptr<double>(u0), dptr<double>(u1), sptr(stream));
   });
+  m.def("gpu_first_step_field",
+        [](const Layout& l, const Layout& src, const Coeffs& c, double tau, std::uintptr_t phi, std::uintptr_t psi,
+           std::uintptr_t u0, std::uintptr_t u1, std::uintptr_t stream) {
+          launch_first_step_field(l, src, c, tau, dptr<const double>(phi), dptr<const double>(psi), dptr<double>(u0),
+                                  dptr<double>(u1), sptr(stream));
+        },
+        py::arg("layout"), py::arg("src"), py::arg("coeffs"), py::arg("tau"), py::arg("phi"), py::arg("psi"),
+        py::arg("u0"), py::arg("u1"), py::arg("stream"), "k_first_step_field (psi = 0: no psi term)");
+  m.def("gpu_energy_depth", &energy_depth, "depth D of k_energy's reduction tree for this layout");
+  m.def("gpu_energy_partials", &energy_partials);
   m.def("gpu_init_two_partials", &init_two_partials);
   m.def("gpu_init_two", [](const Layout& l, const Coeffs& c, std::uintptr_t s, std::uintptr_t u1, std::uintptr_t u2,
                            double ct2, std::uintptr_t partials, std::uintptr_t stream) {
@@ -674,6 +733,14 @@ PYBIND11_MODULE(_C, m) {
         const i64 n = s.problem().N + 1;
         s.set_state(ro_ptr(prev, n * n * n, "prev"), ro_ptr(cur, n * n * n, "cur"), n0);
       }, py::arg("prev"), py::arg("cur"), py::arg("step"))
+      .def("set_initial", [](GpuSolver& s, const darr& phi, py::object psi) {
+        const i64 n = s.problem().N + 1;
+        darr psi_a;
+        if (!psi.is_none()) psi_a = psi.cast<darr>();
+        s.set_initial(ro_ptr(phi, n * n * n, "phi"), psi.is_none() ? nullptr : ro_ptr(psi_a, n * n * n, "psi"));
+      }, py::arg("phi"), py::arg("psi") = py::none())
+      .def("energy", &GpuSolver::energy, py::arg("which") = 0,
+           "discrete energy E^{K-1/2} (which = 0) / E^{1/2} (which = 1, after set_initial); one rank only")
       .def("shell_boxes", &GpuSolver::shell_boxes)
       .def("interior_box", &GpuSolver::interior_box)
       .def("check_steps", &GpuSolver::check_steps)
@@ -755,6 +822,12 @@ PYBIND11_MODULE(_C, m) {
         const i64 n = g.rank(0).problem().N + 1;
         g.set_state(ro_ptr(prev, n * n * n, "prev"), ro_ptr(cur, n * n * n, "cur"), n0);
       }, py::arg("prev"), py::arg("cur"), py::arg("step"))
+      .def("set_initial", [](GpuGroup& g, const darr& phi, py::object psi) {
+        const i64 n = g.rank(0).problem().N + 1;
+        darr psi_a;
+        if (!psi.is_none()) psi_a = psi.cast<darr>();
+        g.set_initial(ro_ptr(phi, n * n * n, "phi"), psi.is_none() ? nullptr : ro_ptr(psi_a, n * n * n, "psi"));
+      }, py::arg("phi"), py::arg("psi") = py::none())
       .def_property_readonly("transport", &GpuGroup::transport)
       .def_property_readonly("graph_enabled", &GpuGroup::graph_enabled)
       .def_property_readonly("world", &GpuGroup::world);

@@ -53,6 +53,87 @@ void cpu_init_first(const Layout& l, const Coeffs& c, const double* s, double* u
   }
 }
 
+void cpu_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
+                          const double* psi, double* u0, double* u1) {
+  W3D_REQUIRE(src.xg == l.xg + 1 && src.yg == l.yg + 1 && src.zg == l.zg + 1 && src.nx == l.nx && src.ny == l.ny &&
+                  src.nz == l.nz && src.gx0 == l.gx0 && src.gy0 == l.gy0 && src.gz0 == l.gz0,
+              "first step: the source layout must be the solve layout's box with one ghost layer more");
+  const i64 N = l.N, P = src.plane, R = src.pitch;
+#pragma omp parallel for schedule(static)
+  for (i64 ix = -l.xg; ix < l.nx + l.xg; ++ix) {
+    const i64 gx = l.gx0 + ix;
+    double* p0 = u0 + (ix + l.xg) * l.plane;
+    double* p1 = u1 + (ix + l.xg) * l.plane;
+    for (i64 q = 0; q < l.plane; ++q) {
+      p0[q] = 0.0;
+      p1[q] = 0.0;
+    }
+    if (gx < 0 || gx > N) continue;
+    for (i64 iy = -l.yg; iy < l.ny + l.yg; ++iy) {
+      const i64 gy = l.gy0 + iy;
+      if (gy < 0 || gy > N) continue;
+      for (i64 iz = -l.zg; iz < l.nz + l.zg; ++iz) {
+        const i64 gz = l.gz0 + iz;
+        if (gz < 0 || gz > N) continue;
+        const i64 o = l.off(ix, iy, iz);
+        const double* f = phi + src.off(ix, iy, iz);
+        const double v = f[0];
+        u0[o] = v;
+        if (gx > 0 && gx < N && gy > 0 && gy < N && gz > 0 && gz < N) {
+          const double lap = c.box ? d2sum_box(v, f[-P], f[P], f[-R], f[R], f[-1], f[1], c.ry, c.rz)
+                                   : d2sum(v, f[-P], f[P], f[-R], f[R], f[-1], f[1]);
+          double w = first_step(v, lap, c.half_lam);
+          if (psi) w = first_step_psi(w, psi[src.off(ix, iy, iz)], tau);
+          u1[o] = w;
+        }
+      }
+    }
+  }
+}
+
+EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double* a, const double* b) {
+  EnergySums out;
+  if (l.nx <= 0 || l.ny <= 0 || l.nz <= 0) return out;
+  W3D_REQUIRE(l.xg >= 1 && l.yg >= 1 && l.zg >= 1, "energy: the layout needs a ghost layer");
+  const i64 N = l.N, P = l.plane, R = l.pitch;
+  const double inv_tau = 1.0 / tau;
+  std::vector<EnergySums> part(static_cast<size_t>(l.nx));
+#pragma omp parallel for schedule(static)
+  for (i64 ix = 0; ix < l.nx; ++ix) {
+    const bool ex = l.gx0 + ix + 1 <= N;
+    EnergySums pl;
+    for (i64 iy = 0; iy < l.ny; ++iy) {
+      const bool ey = l.gy0 + iy + 1 <= N;
+      const double* ra = a + l.off(ix, iy, 0);
+      const double* rb = b + l.off(ix, iy, 0);
+      double kin = 0.0, pot = 0.0, ab = 0.0;
+      for (i64 iz = 0; iz < l.nz; ++iz) {
+        const bool ez = l.gz0 + iz + 1 <= N;
+        const double av = ra[iz], bv = rb[iz];
+        const double v = (bv - av) * inv_tau;
+        const double tk = v * v;
+        const double tx = ex ? ((rb[iz + P] - bv) * (ra[iz + P] - av)) * c.ihx2 : 0.0;
+        const double ty = ey ? ((rb[iz + R] - bv) * (ra[iz + R] - av)) * c.ihy2 : 0.0;
+        const double tz = ez ? ((rb[iz + 1] - bv) * (ra[iz + 1] - av)) * c.ihz2 : 0.0;
+        kin += tk;
+        pot += (tx + ty) + tz;
+        ab += tk + ((std::fabs(tx) + std::fabs(ty)) + std::fabs(tz));
+      }
+      pl.kin += kin;
+      pl.pot += pot;
+      pl.abs += ab;
+    }
+    part[static_cast<size_t>(ix)] = pl;
+  }
+  for (const EnergySums& p : part) {
+    out.kin += p.kin;
+    out.pot += p.pot;
+    out.abs += p.abs;
+  }
+  out.depth = l.nz + l.ny + l.nx;
+  return out;
+}
+
 namespace {
 
 template <bool CHECK, bool BOX>

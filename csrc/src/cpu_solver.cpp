@@ -43,8 +43,62 @@ void global_to_local(const Layout& l, const double* g, double* out) {
   }
 }
 
+void initial_to_local(const Layout& l, const double* g, double* out) {
+  global_to_local(l, g, out);
+  // the six global faces: exact zeros whatever the arrays hold there (homogeneous Dirichlet)
+#pragma omp parallel for schedule(static)
+  for (i64 x = -l.xg; x < l.nx + l.xg; ++x) {
+    const i64 gx = l.gx0 + x;
+    if (gx < 0 || gx > l.N) continue;
+    for (i64 y = -l.yg; y < l.ny + l.yg; ++y) {
+      const i64 gy = l.gy0 + y;
+      if (gy < 0 || gy > l.N) continue;
+      const bool face = gx == 0 || gx == l.N || gy == 0 || gy == l.N;
+      for (i64 z = -l.zg; z < l.nz + l.zg; ++z) {
+        const i64 gz = l.gz0 + z;
+        if (gz >= 0 && gz <= l.N && (face || gz == 0 || gz == l.N)) out[l.off(x, y, z)] = 0.0;
+      }
+    }
+  }
+}
+
+void CpuSolver::set_initial(const double* phi, const double* psi) {
+  W3D_REQUIRE(1 < prob_.K, "resume step must be in [1, K)");
+  init_lay_ = initial_layout(prob_, lay_);
+  for (int k = 0; k < 2; ++k) {
+    const double* g = k == 0 ? phi : psi;
+    init_[k].clear();
+    if (!g) continue;
+    init_[k].assign(static_cast<size_t>(init_lay_.total), 0.0);
+    initial_to_local(init_lay_, g, init_[k].data());
+  }
+  initial_ = true;
+  resume_n_ = 0;
+  resume_[0].clear();
+  resume_[1].clear();
+  runs_ = 0;
+}
+
+EnergySums CpuSolver::energy_sums(int which) const {
+  W3D_REQUIRE(which == 0 || which == 1, "energy: which is 0 (E at K-1/2) or 1 (E at 1/2)");
+  W3D_REQUIRE(runs_ > 0, "energy: no solve has run yet");
+  if (which == 1) {
+    W3D_REQUIRE(initial_, "energy: E(1/2) is kept by solves that start from set_initial");
+    return e_start_;
+  }
+  return cpu_energy(lay_, Coeffs::from(prob_), prob_.tau, field(1).data(), field(0).data());
+}
+
+double CpuSolver::energy(int which) const {
+  const EnergySums e = energy_sums(which);
+  return energy_value(prob_, e.kin, e.pot);
+}
+
 void CpuSolver::set_state(const double* prev, const double* cur, int n0) {
   W3D_REQUIRE(n0 >= 1 && n0 < prob_.K, "resume step must be in [1, K)");
+  initial_ = false;
+  init_[0].clear();
+  init_[1].clear();
   for (int k = 0; k < 2; ++k) {
     resume_[k].assign(static_cast<size_t>(lay_.total), 0.0);
     global_to_local(lay_, k == 0 ? prev : cur, resume_[k].data());
@@ -79,6 +133,10 @@ CpuResult CpuSolver::run() {
   if (resume_n_ > 0) {
     u_[0] = resume_[0];
     u_[1] = resume_[1];
+  } else if (initial_) {
+    cpu_first_step_field(lay_, init_lay_, c, prob_.tau, init_[0].data(), init_[1].empty() ? nullptr : init_[1].data(),
+                         u_[0].data(), u_[1].data());
+    e_start_ = cpu_energy(lay_, c, prob_.tau, u_[0].data(), u_[1].data());
   } else {
     cpu_init_first(lay_, c, s, u_[0].data(), u_[1].data());
   }
@@ -103,6 +161,7 @@ CpuResult CpuSolver::run() {
     std::swap(cur, old);
   }
   final_ = cur;
+  ++runs_;
   r.solve_s = now_s() - t0;
   r.slow_phases[0] = r.init_s;
   r.slow_phases[1] = r.compute_s;

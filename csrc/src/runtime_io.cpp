@@ -64,7 +64,7 @@ std::vector<double> json_numbers(const std::string& text, const std::string& key
 }
 
 // The GLOBAL (N+1)³ field of a dump PREFIX (one file, or PREFIX.rankR of any decomposition); returns its step.
-int load_dump_global(const std::string& prefix, const Problem& p, std::vector<double>& g) {
+int load_dump_global(const std::string& prefix, const Problem& p, std::vector<double>& g, const std::string& what) {
   auto slurp = [](const std::string& path) {
     std::ifstream f(path);
     return std::string((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
@@ -75,9 +75,9 @@ int load_dump_global(const std::string& prefix, const Problem& p, std::vector<do
     bases.push_back(prefix);
   } else {
     meta = slurp(prefix + ".rank0.json");
-    W3D_REQUIRE(!meta.empty(), "resume: no dump " + prefix + ".json or " + prefix + ".rank0.json");
+    W3D_REQUIRE(!meta.empty(), what + ": no dump " + prefix + ".json or " + prefix + ".rank0.json");
     const std::vector<double> w = json_numbers(meta, "world");
-    W3D_REQUIRE(!w.empty() && w[0] >= 1, "resume: dump without a world size");
+    W3D_REQUIRE(!w.empty() && w[0] >= 1, what + ": dump without a world size");
     for (int r = 0; r < static_cast<int>(w[0]); ++r) bases.push_back(prefix + ".rank" + std::to_string(r));
   }
   const i64 n1 = p.N + 1;
@@ -87,38 +87,38 @@ int load_dump_global(const std::string& prefix, const Problem& p, std::vector<do
     const std::string m = slurp(b + ".json");
     const std::vector<double> sh = json_numbers(m, "shape"), of = json_numbers(m, "offset"), st = json_numbers(m, "step"),
                               nn = json_numbers(m, "N");
-    W3D_REQUIRE(sh.size() == 3 && of.size() == 3 && st.size() == 1 && nn.size() == 1, "resume: bad sidecar " + b);
-    W3D_REQUIRE(static_cast<i64>(nn[0]) == p.N, "resume: dump N differs from the run's N");
+    W3D_REQUIRE(sh.size() == 3 && of.size() == 3 && st.size() == 1 && nn.size() == 1, what + ": bad sidecar " + b);
+    W3D_REQUIRE(static_cast<i64>(nn[0]) == p.N, what + ": dump N differs from the run's N");
     // (tau and L too: a checkpoint of another problem would continue from an inconsistent state; the sidecar holds
     // them with 17 significant digits, so they round-trip exactly)
     for (const auto& [key, want] : {std::pair<const char*, double>{"tau", p.tau}, {"L", p.L}}) {
       const std::vector<double> v = json_numbers(m, key);
       W3D_REQUIRE(v.size() == 1 && std::fabs(v[0] - want) <= 1e-15 * std::fabs(want),
-                  std::string("resume: dump ") + key + " differs from the run's " + key);
+                  std::string(what + ": dump ") + key + " differs from the run's " + key);
     }
     // (the box: a sidecar without the key is a cube of edge L, as every dump written before boxes existed)
     {
       const std::vector<double> bx = json_numbers(m, "box"), ll = json_numbers(m, "L");
-      W3D_REQUIRE(bx.empty() || bx.size() == 3, "resume: bad box in sidecar " + b);
+      W3D_REQUIRE(bx.empty() || bx.size() == 3, what + ": bad box in sidecar " + b);
       const double have[3] = {bx.empty() ? ll[0] : bx[0], bx.empty() ? ll[0] : bx[1], bx.empty() ? ll[0] : bx[2]};
       const double want[3] = {p.L, p.edge_y(), p.edge_z()};
       for (int a = 0; a < 3; ++a)
         W3D_REQUIRE(std::fabs(have[a] - want[a]) <= 1e-15 * std::fabs(want[a]),
-                    "resume: dump box differs from the run's box");
+                    what + ": dump box differs from the run's box");
     }
-    W3D_REQUIRE(step < 0 || step == static_cast<int>(st[0]), "resume: rank dumps of different steps");
+    W3D_REQUIRE(step < 0 || step == static_cast<int>(st[0]), what + ": rank dumps of different steps");
     step = static_cast<int>(st[0]);
     const i64 nx = static_cast<i64>(sh[0]), ny = static_cast<i64>(sh[1]), nz = static_cast<i64>(sh[2]);
     const i64 x0 = static_cast<i64>(of[0]), y0 = static_cast<i64>(of[1]), z0 = static_cast<i64>(of[2]);
     W3D_REQUIRE(x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + nx <= n1 && y0 + ny <= n1 && z0 + nz <= n1,
-                "resume: dump box outside the grid");
+                what + ": dump box outside the grid");
     std::ifstream f(b + ".bin", std::ios::binary);
-    W3D_REQUIRE(static_cast<bool>(f), "resume: cannot read " + b + ".bin");
+    W3D_REQUIRE(static_cast<bool>(f), what + ": cannot read " + b + ".bin");
     for (i64 x = 0; x < nx; ++x)
       for (i64 y = 0; y < ny; ++y)
         f.read(reinterpret_cast<char*>(g.data() + ((x0 + x) * n1 + (y0 + y)) * n1 + z0),
                static_cast<std::streamsize>(nz * static_cast<i64>(sizeof(double))));
-    W3D_REQUIRE(static_cast<bool>(f), "resume: short file " + b + ".bin");
+    W3D_REQUIRE(static_cast<bool>(f), what + ": short file " + b + ".bin");
   }
   return step;
 }
@@ -130,6 +130,14 @@ int load_checkpoint(const std::string& prefix, const Problem& p, std::vector<dou
   W3D_REQUIRE(sp == sc - 1, "resume: PREFIX.prev must hold the step before PREFIX.cur");
   W3D_REQUIRE(sc >= 1 && sc < p.K, "resume: checkpoint step " + std::to_string(sc) + " is not before K");
   return sc;
+}
+
+// --initial PREFIX: φ from PREFIX.phi, ψ from PREFIX.psi when that dump exists (psi left empty otherwise)
+void load_initial(const std::string& prefix, const Problem& p, std::vector<double>& phi, std::vector<double>& psi) {
+  load_dump_global(prefix + ".phi", p, phi, "initial");
+  psi.clear();
+  const bool have = std::ifstream(prefix + ".psi.json").good() || std::ifstream(prefix + ".psi.rank0.json").good();
+  if (have) load_dump_global(prefix + ".psi", p, psi, "initial");
 }
 
 }  // namespace wave3d

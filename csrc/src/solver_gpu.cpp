@@ -312,8 +312,9 @@ GpuSolver::~GpuSolver() {
   for (BoxCopyTable& t : pack_tab_) free_box_copy_table(t);
   for (BoxCopyTable& t : unpack_tab_) free_box_copy_table(t);
   if (pk_dev_) (void)hipFree(pk_dev_);
-  for (double* p : {u_[0], u_[1], u_[2], u_[3], d_s_, send_buf_, recv_buf_})
+  for (double* p : {u_[0], u_[1], u_[2], u_[3], d_s_, send_buf_, recv_buf_, init_[0], init_[1]})
     if (p) (void)hipFree(p);
+  if (energy_part_) (void)hipFree(energy_part_);
   if (partials_) (void)hipFree(partials_);
   if (tb_partials_) (void)hipFree(tb_partials_);
   if (errlog_) (void)hipFree(errlog_);
@@ -341,13 +342,96 @@ size_t GpuSolver::device_bytes() const {
          static_cast<size_t>(imax(sch_.halo.packed_doubles, sch_.deep_max) + imax(sch_.halo.packed_doubles, sch_.send_total)) *
              sizeof(double) +
          static_cast<size_t>(n_partials_) * sizeof(Partial) + static_cast<size_t>(sch_.prob.N + 3) * sizeof(double) +
-         static_cast<size_t>(kTbRegions) * kTbLevels * kTbSlots * static_cast<size_t>(n_tb_) * sizeof(Partial);
+         static_cast<size_t>(kTbRegions) * kTbLevels * kTbSlots * static_cast<size_t>(n_tb_) * sizeof(Partial) +
+         ((init_[0] ? 1u : 0u) + (init_[1] ? 1u : 0u)) * static_cast<size_t>(init_lay_.bytes()) +
+         (energy_part_ ? static_cast<size_t>(energy_partials(sch_.lay) + 2) * sizeof(Partial) : 0u);
+}
+
+void GpuSolver::drop_graphs() {
+  if (graph_exec_) W3D_HIP(hipGraphExecDestroy(graph_exec_));
+  graph_exec_ = nullptr;
+  for (hipGraphExec_t& g : xgraph_) {
+    if (g) W3D_HIP(hipGraphExecDestroy(g));
+    g = nullptr;
+  }
+}
+
+void GpuSolver::energy_alloc() const {
+  if (energy_part_) return;
+  W3D_HIP(hipMalloc(&energy_part_, static_cast<size_t>(energy_partials(sch_.lay) + 2) * sizeof(Partial)));
+}
+
+void GpuSolver::set_initial(const double* phi, const double* psi) {
+  W3D_REQUIRE(1 < sch_.prob.K, "resume step must be in [1, K)");
+  W3D_REQUIRE(sch_.mode != Mode::kDeepTb || sch_.prob.K - 1 >= 2, "resume: the multi-rank LDS passes need >= 2 steps left");
+  W3D_REQUIRE(sch_.mode != Mode::kDeep || (sch_.prob.K - 1) % 2 == 0, "resume: two-step passes need an even step count left");
+  int cur = 0;
+  W3D_HIP(hipGetDevice(&cur));
+  W3D_HIP(hipSetDevice(dev_));
+  W3D_HIP(hipDeviceSynchronize());
+  drop_graphs();
+  init_lay_ = initial_layout(sch_.prob, sch_.lay);
+  const size_t bytes = static_cast<size_t>(init_lay_.bytes());
+  std::vector<double> host(static_cast<size_t>(init_lay_.total));
+  for (int k = 0; k < 2; ++k) {
+    const double* g = k == 0 ? phi : psi;
+    if (!g) {
+      if (init_[k]) W3D_HIP(hipFree(init_[k]));
+      init_[k] = nullptr;
+      continue;
+    }
+    initial_to_local(init_lay_, g, host.data());
+    if (!init_[k]) W3D_HIP(hipMalloc(&init_[k], bytes));
+    W3D_HIP(hipMemcpy(init_[k], host.data(), bytes, hipMemcpyHostToDevice));
+  }
+  if (sch_.world == 1) energy_alloc();
+  W3D_HIP(hipSetDevice(cur));
+  initial_ = true;
+  initial_runs_ = 0;
+  resume_n_ = 0;
+  resume_[0] = std::vector<double>();
+  resume_[1] = std::vector<double>();
+}
+
+Partial GpuSolver::energy_sums(int which) const {
+  W3D_REQUIRE(sch_.world == 1, "energy: one rank only (multi-rank: Solver.energy assembles the global fields)");
+  W3D_REQUIRE(which == 0 || which == 1, "energy: which is 0 (E at K-1/2) or 1 (E at 1/2)");
+  W3D_REQUIRE(runs_ > 0 && (!initial_ || initial_runs_ > 0), "energy: no solve has run yet");
+  W3D_REQUIRE(which == 0 || initial_, "energy: E(1/2) is kept by solves that start from set_initial");
+  int cur = 0;
+  W3D_HIP(hipGetDevice(&cur));
+  W3D_HIP(hipSetDevice(dev_));
+  W3D_HIP(hipDeviceSynchronize());
+  energy_alloc();
+  const int n = energy_partials(sch_.lay);
+  if (which == 0) {
+    launch_energy(sch_.lay, coef_, sch_.prob.tau, u_[prev_buf_], u_[final_buf_], energy_part_, nullptr);
+    launch_energy_reduce(energy_part_, n, energy_part_ + n, nullptr);
+  }
+  Partial h;
+  W3D_HIP(hipMemcpy(&h, energy_part_ + n + which, sizeof h, hipMemcpyDeviceToHost));
+  W3D_HIP(hipSetDevice(cur));
+  return h;
+}
+
+double GpuSolver::energy(int which) const {
+  const Partial s = energy_sums(which);
+  return energy_value(sch_.prob, s.x, s.y);
 }
 
 void GpuSolver::set_state(const double* prev, const double* cur, int n0) {
   W3D_REQUIRE(n0 >= 1 && n0 < sch_.prob.K, "resume step must be in [1, K)");
   W3D_REQUIRE(sch_.mode != Mode::kDeepTb || sch_.prob.K - n0 >= 2, "resume: the multi-rank LDS passes need >= 2 steps left");
   W3D_REQUIRE(sch_.mode != Mode::kDeep || (sch_.prob.K - n0) % 2 == 0, "resume: two-step passes need an even step count left");
+  if (initial_) {  // (the two starts replace each other)
+    W3D_HIP(hipDeviceSynchronize());
+    for (double*& p : init_) {
+      if (p) W3D_HIP(hipFree(p));
+      p = nullptr;
+    }
+    initial_ = false;
+  }
+  drop_graphs();
   for (int k = 0; k < 2; ++k) {
     resume_[k].assign(static_cast<size_t>(sch_.lay.total), 0.0);
     global_to_local(sch_.lay, k == 0 ? prev : cur, resume_[k].data());
@@ -405,7 +489,8 @@ void GpuSolver::phase_init() {
     }
   }
   // one rank on the LDS kernel: the first pass starts from the analytic u⁰, u¹ itself (no init kernel, no reads)
-  analytic_ = (sch_.mode == Mode::kFusedSingle || sch_.mode == Mode::kDeepTb) && sch_.analytic_ok() && resume_n_ == 0;
+  analytic_ = (sch_.mode == Mode::kFusedSingle || sch_.mode == Mode::kDeepTb) && sch_.analytic_ok() && resume_n_ == 0 &&
+              !initial_;
   if (resume_n_ > 0) {  // loaded state: u^{n0−1} → buf 0, u^{n0} → buf 1 (ghosts included)
     const size_t bytes = static_cast<size_t>(sch_.lay.bytes());
     timed(kPhaseInit, s0_, [&] {
@@ -413,6 +498,22 @@ void GpuSolver::phase_init() {
       W3D_HIP(hipMemcpyAsync(u_[1], resume_[1].data(), bytes, hipMemcpyHostToDevice, s0_));
     });
     start_n_ = resume_n_;
+  } else if (initial_) {  // user-supplied φ, ψ: u⁰ → buf 0, u¹ → buf 1 (ghosts included) from the device-resident copies
+    timed(kPhaseInit, s0_, [&] {
+      launch_first_step_field(sch_.lay, init_lay_, coef_, sch_.prob.tau, init_[0], init_[1], u_[0], u_[1], s0_);
+    });
+    timed(kPhaseCheck, s0_, [&] {
+      if (energy_part_ && sch_.world == 1) {  // E^{1/2}, kept in its device slot
+        const int ne = energy_partials(sch_.lay);
+        launch_energy(sch_.lay, coef_, sch_.prob.tau, u_[0], u_[1], energy_part_, s0_);
+        launch_energy_reduce(energy_part_, ne, energy_part_ + ne + 1, s0_);
+      }
+      if (is_check_[1]) {
+        launch_error(sch_.lay, u_[1], sch_.full, s, ct_[1], partials_, s0_);
+        launch_reduce(partials_, error_blocks(sch_.lay, sch_.full), errlog_ + 1, s0_);
+      }
+    });
+    start_n_ = 1;
   } else if (analytic_) {
     start_n_ = 1;
   } else if (sch_.opt.init2 && K >= 2) {
@@ -925,6 +1026,7 @@ RunResult GpuSolver::run() {
   r.solve_s = now_s() - t0;
   collect_phases(r);
   ++runs_;
+  if (initial_) ++initial_runs_;
   return r;
 }
 
@@ -967,6 +1069,7 @@ std::vector<RunResult> GpuSolver::run_batch(int n) {
   const double dt = (now_s() - t0) / n;
   xsolves_ += static_cast<unsigned>(n);
   runs_ += n;
+  if (initial_) initial_runs_ += n;
   for (int i = 0; i < n; ++i) {
     RunResult r;
     decode_log(hbatch_ + static_cast<size_t>(i) * slot, nsrc, r);
@@ -1273,6 +1376,7 @@ GpuGroup::GpuGroup(const Problem& prob, const SolverOptions& opt, int world, con
   // (sdma: the flag waits of one rank's stream are released by other ranks' streams, so the group enqueues eagerly in
   // an order where every wait is issued after the write it waits for — see enqueue)
   graph_ = opt.graph && !opt.timers && !opt.debug_sync && (world == 1 || multistream_capture_safe()) && !o.sdma;
+  graph0_ = graph_;
   W3D_HIP(hipStreamCreateWithFlags(&gs_, hipStreamNonBlocking));
   W3D_HIP(hipEventCreateWithFlags(&fork_, hipEventDisableTiming));
   W3D_HIP(hipEventCreateWithFlags(&all_packed_, hipEventDisableTiming));
@@ -1299,6 +1403,18 @@ GpuGroup::~GpuGroup() {
 void GpuGroup::set_state(const double* prev, const double* cur, int n0) {
   for (auto& r : ranks_) r->set_state(prev, cur, n0);
   graph_ = false;  // (the state upload is a pageable host copy: eager runs)
+}
+
+void GpuGroup::set_initial(const double* phi, const double* psi) {
+  int cur = 0;
+  W3D_HIP(hipGetDevice(&cur));
+  for (auto& r : ranks_) r->set_initial(phi, psi);
+  W3D_HIP(hipSetDevice(cur));
+  if (multi_) return;  // (every rank captures its own solve)
+  // nothing host-side per solve: the group solve is captured again, with the first-step kernels in it
+  if (exec_) W3D_HIP(hipGraphExecDestroy(exec_));
+  exec_ = nullptr;
+  graph_ = graph0_;
 }
 
 std::vector<int> GpuGroup::comm_counts() const {

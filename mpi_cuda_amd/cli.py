@@ -49,6 +49,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dump", default="", help="write u^K to PREFIX[.rankR].bin/.json")
     ap.add_argument("--checkpoint", default="", help="write u^{K-1}, u^K to PREFIX.prev / PREFIX.cur dumps")
     ap.add_argument("--resume", default="", help="continue from a --checkpoint PREFIX (any backend/transport)")
+    ap.add_argument("--initial", default="", metavar="PREFIX",
+                    help="solve from your own initial data: u(.,0) from the dump PREFIX.phi and, if present, u_t(.,0) "
+                         "from PREFIX.psi (backends hip and cpu)")
+    ap.add_argument("--energy", action="store_true",
+                    help="print the discrete energy E(1/2), E(K-1/2) and its drift (with --initial)")
     ap.add_argument("--force", action="store_true", help="run even if the CFL condition is violated")
     ap.add_argument("--quiet", action="store_true")
     return ap
@@ -70,6 +75,10 @@ def main(argv=None) -> int:
         a.L = box[0]
     elif a.L is None:
         a.L = 1.0
+    if a.initial and a.resume:
+        ap.error("--initial and --resume exclude each other")
+    if a.energy and not a.initial:
+        ap.error("--energy needs --initial (E(1/2) is kept by solves that start from it)")
     import torch
     import torch.distributed as dist
 
@@ -116,6 +125,25 @@ def main(argv=None) -> int:
                       f"{list(spec.edges)}", file=sys.stderr)
                 return 2
         s.set_state(prev, cur, int(meta_c["step"]))
+    if a.initial:
+        fields = []
+        for part in ("phi", "psi"):
+            base = f"{a.initial}.{part}"
+            if part == "psi" and not (os.path.exists(base + ".json") or os.path.exists(base + ".rank0.json")):
+                fields.append(None)  # (no PREFIX.psi sidecar: u_t(.,0) = 0; a partial dump fails in load)
+                continue
+            f, m = dumpio.load(base)
+            for key, want in (("N", a.N), ("tau", a.tau), ("L", a.L)):  # (the checks --resume makes)
+                got = m.get(key)
+                if got is None or not math.isclose(float(got), float(want), rel_tol=1e-15, abs_tol=0.0):
+                    print(f"wave3d: initial: dump {key} = {got} differs from the run's {want}", file=sys.stderr)
+                    return 2
+            if any(not math.isclose(g, w, rel_tol=1e-15, abs_tol=0.0) for g, w in zip(dumpio.box_of(m), spec.edges)):
+                print(f"wave3d: initial: dump box {list(dumpio.box_of(m))} differs from the run's "
+                      f"{list(spec.edges)}", file=sys.stderr)
+                return 2
+            fields.append(f)
+        s.set_initial(*fields)
     r = None
     times = []
     for i in range(a.warmup + a.repeat):
@@ -135,6 +163,9 @@ def main(argv=None) -> int:
                   f"ranks={s.world} decomp={'x'.join(map(str, s.dims))}")
             for line in r.lines():
                 print(line)
+        if a.energy:
+            e_start, e_end = s.energy(1), s.energy(0)
+            print(f"Energy: E(1/2) = {e_start:.15e}, E(K-1/2) = {e_end:.15e}, drift = {abs(e_end - e_start) / e_start:.3e}")
         cells = spec.cell_updates if not a.resume else float(a.N) ** 3 * (a.K - int(meta_c["step"]))
         print(f"Total time: {best:.6f} s, {cells / best / 1e9:.2f} GCell/s")
         ph = r.extra.get("phases")
@@ -145,6 +176,7 @@ def main(argv=None) -> int:
                 json.dump({"backend": s.backend, "transport": s.transport, "N": a.N, "tau": a.tau, "K": a.K, "L": a.L,
                            **({"box": list(spec.edges)} if spec.is_box else {}), "ranks": s.world, "dims": list(s.dims), "solve_s": best,
                            "gcell_per_s": gcell_per_s(a.N, a.K, best),
+                           **({"energy_start": e_start, "energy_end": e_end} if a.energy else {}),
                            "steps": [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]}, f)
     if a.dump or a.checkpoint:
         def write(prefix, which):

@@ -207,6 +207,26 @@ def oracle_errors(spec: ProblemSpec, steps: list[int] | None = None, dps: int = 
     return out
 
 
+def oracle_energy(spec: ProblemSpec, n: int, dps: int = 50) -> float:
+    """Discrete energy E^{n+1/2} of the eigenmode solve in closed form (cpu.hpp ``cpu_energy`` has the definition).
+    u^n = cos(nθ)·φ and φ is an eigenfunction of −Δ_h with eigenvalue λ, so (summation by parts, zero boundary)
+
+        E^{n+1/2} = ½‖φ‖²_V·[(cos((n+1)θ) − cos(nθ))²/τ² + λ·cos((n+1)θ)·cos(nθ)],   ‖φ‖²_V = V·(N/2)³, V = hx·hy·hz
+
+    with λ, θ as in ``oracle_errors``; evaluated in ``dps``-digit arithmetic. It does not depend on n."""
+    import mpmath as mp
+
+    mp.mp.dps = dps
+    N = spec.N
+    tau = mp.mpf(spec.tau)
+    hs = [mp.mpf(e) / N for e in spec.edges]
+    lam = 4 * mp.sin(mp.pi / (2 * N)) ** 2 * mp.fsum(1 / h**2 for h in hs)
+    theta = mp.acos(1 - tau**2 * lam / 2)
+    c0, c1 = mp.cos(n * theta), mp.cos((n + 1) * theta)
+    norm2 = hs[0] * hs[1] * hs[2] * (mp.mpf(N) / 2) ** 3
+    return float(norm2 / 2 * ((c1 - c0) ** 2 / tau**2 + lam * c1 * c0))
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # independent PyTorch fp64 reference solver (second oracle; runs on CPU or GPU)
 # ----------------------------------------------------------------------------------------------------------------

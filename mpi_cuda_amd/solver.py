@@ -115,6 +115,7 @@ class Solver:
         self.backend, self.transport = _resolve(backend, transport, world)
         self.decomp = decomp
         self._impl = None
+        self._initial = None  # (set_initial's global phi, psi: a group's E(1/2) is computed from them on the host)
         if runtime not in ("inproc", "process"):
             raise ValueError("runtime is 'inproc' (this process) or 'process' (a native bin/wave3d rank process)")
         self.runtime = runtime
@@ -345,6 +346,7 @@ class Solver:
             raise ValueError("the torch reference solver has no resume")
         if self.runtime == "process":
             raise ValueError("runtime='process' has no resume from Python (use bin/wave3d --resume)")
+        self._initial = None  # (the loaded state takes the initial data's place)
         if self.transport == "torch":
             to_t = (lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a)))
             self._impl.set_state(to_t(prev), to_t(cur), int(step))
@@ -352,6 +354,66 @@ class Solver:
         to_np = (lambda a: np.ascontiguousarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a,
                                                 dtype=np.float64).reshape(-1))
         self._impl.set_state(to_np(prev), to_np(cur), int(step))
+
+    def set_initial(self, phi, psi=None) -> None:
+        """Solve from user-supplied initial data: ``phi`` = u(·,0) and optional ``psi`` = u_t(·,0) (None: 0), GLOBAL
+        (N+1)³ float64 arrays or tensors as ``set_state`` takes its fields. Values on the six faces are ignored (u⁰
+        and u¹ are 0 there). Every following run() starts from u⁰ = φ, u¹ = φ + τψ + (τ²/2)Δ_h φ (stencil.hpp
+        ``first_step`` / ``first_step_psi``) and continues to K. The HIP backend keeps φ, ψ on the device, so the
+        solve stays graph-captured and ``run_batch`` pipelined. The error columns of the result then are the
+        difference from the eigenmode sin·sin·sin·cos(a_t t), which means nothing for other data: use ``energy``.
+        Backends hip and cpu; it and ``set_state`` replace each other."""
+        import numpy as np
+
+        if self.runtime == "process":
+            raise ValueError("runtime='process' has no initial data from Python (use bin/wave3d --initial)")
+        if self.backend == "torch" or self.transport == "torch":
+            raise ValueError("set_initial needs the native hip or cpu backend")
+        n = self.spec.N + 1
+
+        def to_np(a):
+            a = np.ascontiguousarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+            if a.size != n * n * n:
+                raise ValueError(f"set_initial: expected a global ({n}, {n}, {n}) field, got shape {a.shape}")
+            return a.reshape(-1)
+
+        self._initial = (to_np(phi), None if psi is None else to_np(psi))
+        self._impl.set_initial(*self._initial)
+
+    def energy(self, which: int = 0) -> float:
+        """Discrete energy of the last run(): ``which=0`` E^{K−1/2} from the retained u^{K−1}, u^K; ``which=1``
+        E^{1/2} from u⁰, u¹ (after ``set_initial``). Leapfrog conserves it exactly in exact arithmetic (cpu.hpp
+        ``cpu_energy`` has the formula). One native rank computes it itself (hip: ``k_energy``); a group or several
+        in-process ranks run ``cpu_energy`` on the assembled global fields; the ranks of a process-per-rank job cannot
+        be assembled here and are refused."""
+        import numpy as np
+
+        if self.runtime == "process":
+            raise ValueError("runtime='process' has no energy from Python (use bin/wave3d --energy)")
+        if self.backend == "torch" or self.transport == "torch":
+            raise ValueError("energy needs the native hip or cpu backend")
+        C = load()
+        if not isinstance(self._impl, C.GpuGroup) and self.world == 1:
+            return float(self._impl.energy(int(which)))
+        if not isinstance(self._impl, C.GpuGroup):
+            raise ValueError("energy: the ranks of a process-per-rank job cannot be assembled here (global_field "
+                             "needs one rank or an in-process group): run one rank, or a group in one process")
+        prob = self.spec.native()
+        lay = C.make_layout(prob, C.rank_box(prob, C.Dims(1, 1, 1), 0))
+        if which == 0:
+            # (global → padded local array; the faces it zeroes hold 0 already)
+            a, b = (C.initial_to_local(lay, np.ascontiguousarray(self.global_field(w).numpy()).reshape(-1))
+                    for w in (1, 0))
+        else:
+            init = self._initial
+            if init is None:
+                raise ValueError("energy: E(1/2) is kept by solves that start from set_initial")
+            src = C.initial_layout(prob, lay)
+            a, b = np.zeros(lay.total), np.zeros(lay.total)
+            C.cpu_first_step_field(lay, src, C.Coeffs.from_problem(prob), self.spec.tau,
+                                   C.initial_to_local(src, init[0]),
+                                   None if init[1] is None else C.initial_to_local(src, init[1]), a, b)
+        return float(C.cpu_energy(prob, lay, a, b)["E"])
 
     @property
     def native(self):

@@ -448,6 +448,21 @@ PYBIND11_MODULE(_C, m) {
         py::arg("u0"), py::arg("u1"), py::arg("stream"), "k_first_step_field (psi = 0: no psi term)");
   m.def("gpu_energy_depth", &energy_depth, "depth D of k_energy's reduction tree for this layout");
   m.def("gpu_energy_partials", &energy_partials);
+  m.def("gpu_energy",
+        [](const Layout& l, const Coeffs& c, double tau, std::uintptr_t a, std::uintptr_t b, std::uintptr_t partials,
+           std::uintptr_t out, std::uintptr_t stream) {
+          launch_energy(l, c, tau, dptr<const double>(a), dptr<const double>(b), dptr<Partial>(partials), sptr(stream));
+          launch_energy_reduce(dptr<const Partial>(partials), energy_partials(l), dptr<Partial>(out), sptr(stream));
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("tau"), py::arg("a"), py::arg("b"), py::arg("partials"),
+        py::arg("out"), py::arg("stream"),
+        "k_energy of a = u^n, b = u^{n+1} into gpu_energy_partials(layout) partials, then k_energy_reduce of them "
+        "into out[0] = (kinetic sum, potential sum)");
+  m.def("gpu_energy_reduce",
+        [](std::uintptr_t partials, int n, std::uintptr_t out, std::uintptr_t stream) {
+          launch_energy_reduce(dptr<const Partial>(partials), n, dptr<Partial>(out), sptr(stream));
+        },
+        py::arg("partials"), py::arg("n"), py::arg("out"), py::arg("stream"), "k_energy_reduce alone");
   m.def("gpu_init_two_partials", &init_two_partials);
   m.def("gpu_init_two", [](const Layout& l, const Coeffs& c, std::uintptr_t s, std::uintptr_t u1, std::uintptr_t u2,
                            double ct2, std::uintptr_t partials, std::uintptr_t stream) {

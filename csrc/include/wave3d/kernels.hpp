@@ -74,11 +74,10 @@ void launch_leapfrog2(const Layout& l, const Coeffs& c, const double* prev, cons
                       const Leapfrog2Tiling& t, hipStream_t stream, i64 sx0 = 1, i64 sx1 = 0);
 
 // Deep temporal blocking: S = 2..4 leapfrog steps in one pass, all intermediate levels in LDS (32 × 32 (y,z) tiles
-// marching in x (or in x chunks when the tiles alone do not fill the GPU), one workgroup per CU). Reads u^{n−1}, u^n; writes u^{n+S−1} into out1 and u^{n+S} into out2: 32/S
-// compulsory bytes per node-step. Same preconditions as launch_leapfrog2 with S−1 stage-1 planes beyond the box.
-// Error check of u^{n+k} when bit k−1 of `check_mask` is set (ct[k−1] = its time factor); stage k's partials go to
-// partials + (k−1)·level_stride (0: leapfrog_tb_partials(), the launch's block count). analytic_start: the pass starts at n = 1 from u⁰ = φ and u¹ computed in
-// the kernel (init_first's formulas, bit-identical), prev/cur are not read: it writes u^S, u^{S+1} with no HBM reads.
+// marching in x (or in x chunks when the tiles alone do not fill the GPU), one workgroup per CU). Reads u^{n−1}, u^n;
+// writes u^{n+S−1} into out1 and u^{n+S} into out2: 32/S compulsory bytes per node-step. Same preconditions as
+// launch_leapfrog2 with S−1 stage-1 planes beyond the box. The launch arguments: PassArgs below.
+//
 // Slab peer-push transport of an LDS pass (x faces only; every slab rank has the same plane geometry, so a plane's
 // in-plane offsets are the same on both sides). The pass
 //   * marches the upper face segment [x1 − T, x1) first, then [x0, x1 − T) (faces_first), so both face regions are
@@ -133,31 +132,81 @@ void l2_flush_all(hipStream_t stream);
 void leapfrog_tb_prepare(bool push = false);  // push: also the push-transport instantiations
 size_t leapfrog_tb_lds_bytes(int stages);
 int leapfrog_tb_partials(const Layout& l, const LBox& box, const LeapfrogTbTiling& t);
-void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
-                        double* out2, const LBox& box, const double* d_s, const double* ct, int check_mask,
-                        Partial* partials, const LeapfrogTbTiling& t, hipStream_t stream,
-                        const LBox& real = tb_default_real(), bool analytic_start = false, int level_stride = 0,
-                        int grid_blocks = 0, const TbPush* push = nullptr, const TbPush* push_dev = nullptr,
-                        const TbPack* pack = nullptr, const TbPack* pack_dev = nullptr);
+
+// What a launch of an LDS S-step pass (S = tiling.stages) takes besides the layout, the coefficients, its box or boxes
+// and the stream.
+struct PassArgs {
+  const double *prev = nullptr, *cur = nullptr;  // u^{n−1}, u^n
+  double *out1 = nullptr, *out2 = nullptr;       // u^{n+S−1}, u^{n+S}: four distinct buffers
+  const double* d_s = nullptr;                   // sin table, global index −1..N+1
+  double ct[5] = {0, 0, 0, 0, 0};                // ct[k−1]: the time factor of u^{n+k}
+  int check_mask = 0;            // bit k−1: error check of u^{n+k} ...
+  Partial* partials = nullptr;   // ... whose partials go to partials + (k−1)·level_stride (nullptr: no check)
+  int level_stride = 0;          // 0: the launch's block count (leapfrog_tb_partials())
+  // > 0: a padded grid (several launches sharing one level's partial slots, each of grid_blocks entries): the extra
+  // workgroups have no tile and write (0, 0) partials, so every slot entry a reduction reads is written
+  int grid_blocks = 0;
+  LeapfrogTbTiling tiling;
+  LBox real = tb_default_real();  // stage-real ranges (tiling.hpp)
+  // the pass starts at n = 1 from u⁰ = φ and u¹ computed in the kernel (init_first's formulas, bit-identical): prev /
+  // cur are not read, it writes u^S, u^{S+1} with no HBM reads
+  bool analytic_start = false;
+  // slab peer-push transport and fused z-face pack (k_leapfrog_tb only): the host copy, which the launcher reads, and
+  // the same entry in device memory, which the kernel reads
+  const TbPush *push = nullptr, *push_dev = nullptr;
+  const TbPack *pack = nullptr, *pack_dev = nullptr;
+};
+
+// What both launchers fill alike in their kernel parameters (TbParams / P2Params: the field names agree), after the
+// plan set p.nblocks: buffers from the plane the x ghosts start at, coefficients, check mask and partials,
+// the grid padded to grid_blocks (xper stays the active blocks' per-XCD share: else the remap would hand every tile to
+// the first XCDs — measured: a slab rank's 256 tiles on 4 of 8 XCDs, passes 2.2x slower). false: nothing to launch.
+template <class Params>
+bool fill_pass_params(Params& p, const Layout& l, const Coeffs& c, const PassArgs& a, const char* name) {
+  W3D_REQUIRE(a.out1 != a.out2 && (a.analytic_start || (a.prev != a.out1 && a.prev != a.out2 && a.cur != a.out1 &&
+                                                         a.cur != a.out2)),
+              std::string(name) + " needs four distinct buffers");
+  if (p.nblocks == 0) return false;
+  const LeapfrogTbTiling& t = a.tiling;
+  if (a.grid_blocks > 0) {
+    W3D_REQUIRE(a.grid_blocks >= p.nblocks && (!t.xcd_remap || a.grid_blocks % 8 == 0),
+                std::string(name) + ": bad grid_blocks");
+    p.nblocks = a.grid_blocks;
+  }
+  const i64 kb = (l.xg - 1) * l.plane;  // x base only: in-plane offsets are plane-relative (non-negative)
+  p.prev = a.analytic_start ? nullptr : a.prev + kb;
+  p.cur = a.analytic_start ? nullptr : a.cur + kb;
+  p.out1 = a.out1 + kb;
+  p.out2 = a.out2 + kb;
+  p.s = a.d_s;
+  p.tau2 = c.lam;  // τ²/h² and τ²/(2h²): the coefficients of d2sum
+  p.half_tau2 = c.half_lam;
+  p.ry = c.ry;
+  p.rz = c.rz;
+  p.check_mask = a.partials != nullptr ? (a.check_mask & ((1 << t.stages) - 1)) : 0;
+  p.partials = p.check_mask != 0 ? a.partials : nullptr;
+  W3D_REQUIRE(a.level_stride == 0 || a.level_stride >= p.nblocks,
+              std::string(name) + ": level stride below the block count");
+  p.lstride = a.level_stride > 0 ? a.level_stride : p.nblocks;
+  constexpr int nct = static_cast<int>(sizeof(p.ct) / sizeof(p.ct[0]));
+  for (int k = 0; k < nct; ++k) p.ct[k] = k < t.stages ? a.ct[k] : 0.0;
+  return true;
+}
+
+// Dispatches to the pair-tiled pass where pass_kernel (pass_grid.hpp) says so.
+void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const LBox& box, const PassArgs& a, hipStream_t stream);
 
 // The pair-tiled S-step pass (kernels_leapfrog_p2.hip): the same contract as launch_leapfrog_tb for boxes inside the
 // rank's y/z range that start and end on whole 16-byte pairs (leapfrog_p2_supported) and S = 2..5 (analytic start:
-// 2..4); no push / fused pack. launch_leapfrog_tb dispatches to it when tiling.p2 is set and it applies.
-// launch_leapfrog_p2_boxes: up to kP2MaxBoxes boxes in ONE launch (one grid, the x-chunk target shared by work), for the
-// overlapped schedules' shell boxes; their partials share one slot of `grid_blocks` entries.
+// 2..4); no push / fused pack. Up to kP2MaxBoxes boxes in ONE launch (one grid, the x-chunk target shared by work), for
+// the overlapped schedules' shell boxes; their partials share one slot of `grid_blocks` entries.
 int leapfrog_p2_partials(const Layout& l, const LBox& box, const LeapfrogTbTiling& t);
 // (tests) the pair-tiled pass's thread → position table for S stages (kNT descriptors: (a+2) | (b+2)<<8 | lv<<16 |
 // kind<<20) and its geometry {E, HY, HZ, PZ, tile, LDS bytes at xlen 512 (pass, analytic start), max xlen (same)}
 std::vector<int> leapfrog_p2_table(int stages, std::vector<long>* geometry = nullptr);
 void leapfrog_p2_prepare();
-void launch_leapfrog_p2(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
-                        double* out2, const LBox& box, const double* d_s, const double* ct, int check_mask,
-                        Partial* partials, const LeapfrogTbTiling& t, hipStream_t stream, const LBox& real,
-                        bool analytic_start, int level_stride = 0, int grid_blocks = 0);
-void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
-                              double* out2, const LBox* boxes, int nbox, const double* d_s, const double* ct,
-                              int check_mask, Partial* partials, const LeapfrogTbTiling& t, hipStream_t stream,
-                              const LBox& real, bool analytic_start, int level_stride = 0, int grid_blocks = 0);
+void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const LBox* boxes, int nbox, const PassArgs& a,
+                              hipStream_t stream);
 
 // Error of a stored field vs φ·ct over `box` (step 1 / standalone check). Writes leapfrog-compatible partials and
 // returns how many.

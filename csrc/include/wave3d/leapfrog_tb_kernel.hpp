@@ -815,52 +815,16 @@ __global__ __launch_bounds__(NT) void k_leapfrog_tb(const TbParams p) {
   }
 }
 
-struct TbPlan {
-  TbParams prm{};
-  int nblocks = 0;
-};
-
 // `real`: per axis, the local range where stage values are real (outside: Dirichlet 0 / unused); an axis with lo > hi
 // takes the default (x: the compute box; y, z: the whole allocation, i.e. no restriction besides the global interior).
-inline TbPlan make_plan_tb(const Layout& l, const LBox& b, const LeapfrogTbTiling& t, LBox real) {
+// Returns the kernel parameters the box decides; nblocks = 0: an empty box.
+inline TbParams make_plan_tb(const Layout& l, const LBox& b, const LeapfrogTbTiling& t, LBox real) {
   W3D_REQUIRE(t.stages >= 2 && t.stages <= 4, "leapfrog_tb: stages must be 2, 3 or 4");
   W3D_REQUIRE((t.threads == 768 || t.threads == 1024) && (t.init_threads == 768 || t.init_threads == 1024),
               "leapfrog_tb: threads must be 768 or 1024");
-  const LBox full = compute_box(l);
-  if (real.x0 > real.x1) {
-    real.x0 = full.x0;
-    real.x1 = full.x1;
-  }
-  if (real.y0 > real.y1) {
-    real.y0 = -l.yg;
-    real.y1 = l.ny + l.yg;
-  }
-  if (real.z0 > real.z1) {
-    real.z0 = -l.zg;
-    real.z1 = l.nz + l.zg;
-  }
-  W3D_REQUIRE(b.x0 >= full.x0 && b.x1 <= full.x1 && b.y0 >= full.y0 && b.y1 <= full.y1 && b.z0 >= full.z0 &&
-                  b.z1 <= full.z1,
-              "leapfrog_tb box outside the compute box");
   W3D_REQUIRE(l.N < (1 << 20) && l.plane < (1 << 28), "leapfrog_tb: plane too large for 28-bit in-plane offsets");
-  const i64 S = t.stages;
-  // per axis: u^{n+k} (k < S) is read up to S−k nodes beyond the box, so its values there must be real (the `real`
-  // range) unless they lie beyond the global boundary (structural zeros); u^n is read S nodes beyond the box, within
-  // the allocation (ghost depth g) unless beyond the global boundary
-  auto axis_ok = [&](i64 b0, i64 b1, i64 r0, i64 r1, i64 g0, i64 n, i64 g, const char* ax) {
-    const bool lo_ok = r0 <= b0 - (S - 1) || g0 + r0 <= 1;
-    const bool hi_ok = r1 >= b1 + (S - 1) || g0 + r1 >= l.N;
-    W3D_REQUIRE(lo_ok && hi_ok, std::string("leapfrog_tb: stage-1 range does not cover the box halo in ") + ax);
-    W3D_REQUIRE(g0 + b0 - S <= 0 || b0 - S >= -g, std::string("leapfrog_tb: halo deeper than the ghosts in ") + ax);
-    W3D_REQUIRE(g0 + b1 + S - 1 >= l.N || b1 + S - 1 < n + g,
-                std::string("leapfrog_tb: halo deeper than the ghosts in ") + ax);
-    W3D_REQUIRE(r0 >= -g && r1 <= n + g, std::string("leapfrog_tb: real range outside the allocation in ") + ax);
-  };
-  axis_ok(b.x0, b.x1, real.x0, real.x1, l.gx0, l.nx, l.xg, "x");
-  axis_ok(b.y0, b.y1, real.y0, real.y1, l.gy0, l.ny, l.yg, "y");
-  axis_ok(b.z0, b.z1, real.z0, real.z1, l.gz0, l.nz, l.zg, "z");
-  TbPlan pl;
-  TbParams& p = pl.prm;
+  real = pass_box_check(l, b, t.stages, real, "leapfrog_tb", true);  // (pass_grid.hpp)
+  TbParams p{};
   p.plane = l.plane;
   p.pitch = l.pitch;
   p.zs = l.zs;
@@ -891,7 +855,7 @@ inline TbPlan make_plan_tb(const Layout& l, const LBox& b, const LeapfrogTbTilin
   p.y1 = static_cast<int>(b.y1);
   p.z0 = static_cast<int>(b.z0);
   p.z1 = static_cast<int>(b.z1);
-  if (b.x1 <= b.x0 || b.y1 <= b.y0 || b.z1 <= b.z0) return pl;
+  if (b.x1 <= b.x0 || b.y1 <= b.y0 || b.z1 <= b.z0) return p;
   // the tile grid and the x chunks: the host-side arithmetic that also sizes the partial slots (pass_grid.hpp)
   const PassBoxGrid g = tb_box_grid(b, t);
   p.nty = g.nty;
@@ -899,13 +863,12 @@ inline TbPlan make_plan_tb(const Layout& l, const LBox& b, const LeapfrogTbTilin
   p.xlen = g.xlen;
   p.nxc = g.nxc;
   const int tiles = g.tiles();
-  pl.nblocks = tb_round(g.blocks(), t);
-  p.nblocks = pl.nblocks;
+  p.nblocks = pass_round(g.blocks(), t);
   p.xcd_remap = t.xcd_remap ? 1 : 0;
-  p.xper = pl.nblocks / 8;
+  p.xper = p.nblocks / 8;
   // blocked XCD ownership when the tile grid splits into 8 equal blocks (one per XCD), the squarest such block
   p.bby = p.bbz = 0;
-  if (t.xcd_remap && t.xcd_blocks && p.nxc == 1 && tiles == pl.nblocks && tiles % 8 == 0) {
+  if (t.xcd_remap && t.xcd_blocks && p.nxc == 1 && tiles == p.nblocks && tiles % 8 == 0) {
     const int per = tiles / 8;
     int best = 1 << 30;
     for (int by = 1; by <= per; ++by) {
@@ -920,7 +883,7 @@ inline TbPlan make_plan_tb(const Layout& l, const LBox& b, const LeapfrogTbTilin
       }
     }
   }
-  return pl;
+  return p;
 }
 
 template <int NT>

@@ -60,7 +60,8 @@ inline PassBoxGrid p2_box_grid(const LBox& b, const LeapfrogTbTiling& t, int S) 
   return g;  // (unrounded: the launch grid rounds the sum of its boxes up to whole XCD shares)
 }
 
-inline int p2_round(int blocks, const LeapfrogTbTiling& t) {
+// (either kernel) a launch grid: whole XCD shares under xcd_remap
+inline int pass_round(int blocks, const LeapfrogTbTiling& t) {
   return t.xcd_remap ? static_cast<int>(round_up(blocks, 8)) : blocks;
 }
 
@@ -99,7 +100,7 @@ inline P2LaunchGrid p2_launch_grid(const LBox* boxes, int n, const LeapfrogTbTil
     pl.xlen_max = static_cast<int>(imax(pl.xlen_max, g.xlen));
   }
   pl.nactive = blk;
-  pl.nblocks = blk == 0 ? 0 : p2_round(blk, t);
+  pl.nblocks = blk == 0 ? 0 : pass_round(blk, t);
   return pl;
 }
 
@@ -109,7 +110,7 @@ inline int p2_partials(const LBox& box, const LeapfrogTbTiling& t) {
   // chunk's x sin table — ADVICE r5: S = 2 alone undercounted boxes longer than the S = 5 chunk)
   if (box.x1 <= box.x0 || box.y1 <= box.y0 || box.z1 <= box.z0) return 0;
   int n = 0;
-  for (int S = 2; S <= 5; ++S) n = static_cast<int>(imax(n, p2_round(p2_box_grid(box, t, S).blocks(), t)));
+  for (int S = 2; S <= 5; ++S) n = static_cast<int>(imax(n, pass_round(p2_box_grid(box, t, S).blocks(), t)));
   return n;
 }
 
@@ -131,17 +132,57 @@ inline PassBoxGrid tb_box_grid(const LBox& b, const LeapfrogTbTiling& t) {
   }
   return g;
 }
-inline int tb_round(int blocks, const LeapfrogTbTiling& t) {
-  return t.xcd_remap ? static_cast<int>(round_up(blocks, 8)) : blocks;
-}
 
 // ---- either kernel
+
+// Which kernel family runs a launch of `stages` steps over `box`: the pair-tiled pass where tiling.p2 asks for it and
+// it applies — a box it takes (leapfrog_p2_supported), no push transport and no fused pack (both live in
+// k_leapfrog_tb), an analytic start of at most 4 steps — else k_leapfrog_tb, which then refuses S = 5. The launcher
+// dispatches by this rule, and everything that sizes or plans for a launch (GpuSolver, schedule.cpp) asks it too.
+enum class PassKernel { kTb, kP2 };
+inline PassKernel pass_kernel(const Layout& l, const LBox& box, int stages, bool p2, bool analytic_start, bool push,
+                              bool pack) {
+  return p2 && !push && !pack && leapfrog_p2_supported(l, box, stages) && !(analytic_start && stages > 4)
+             ? PassKernel::kP2
+             : PassKernel::kTb;
+}
+
+// The checks a box must pass before either kernel marches it, per axis (g0: the rank's global offset, n: its nodes,
+// g: its ghost depth): u^{n+k} (k < S) is read up to S−k nodes beyond the box, so its values there must be real (the
+// `real` range) unless they lie beyond the global boundary (structural zeros); u^n is read S nodes beyond the box,
+// within the allocation unless beyond the global boundary. Returns `real` with its defaulted axes (lo > hi) resolved:
+// x: the compute box; y, z: the whole allocation. yz_real: k_leapfrog_tb, which has y/z real ranges and takes boxes of
+// the compute box only; the pair-tiled pass has neither (its box rule is leapfrog_p2_supported), so there only the
+// halo depth is checked in y and z. `name` starts the messages.
+inline LBox pass_box_check(const Layout& l, const LBox& b, i64 S, LBox real, const char* name, bool yz_real) {
+  const LBox full = compute_box(l);
+  auto msg = [&](const char* what, const char* ax) { return std::string(name) + what + ax; };
+  if (real.x0 > real.x1) real.x0 = full.x0, real.x1 = full.x1;
+  if (real.y0 > real.y1) real.y0 = -l.yg, real.y1 = l.ny + l.yg;
+  if (real.z0 > real.z1) real.z0 = -l.zg, real.z1 = l.nz + l.zg;
+  W3D_REQUIRE(!yz_real || (b.x0 >= full.x0 && b.x1 <= full.x1 && b.y0 >= full.y0 && b.y1 <= full.y1 &&
+                           b.z0 >= full.z0 && b.z1 <= full.z1),
+              msg(" box outside the compute box", ""));
+  auto axis = [&](i64 b0, i64 b1, i64 r0, i64 r1, i64 g0, i64 n, i64 g, bool ranged, const char* ax) {
+    W3D_REQUIRE((g0 + b0 - S <= 0 || b0 - S >= -g) && (g0 + b1 + S - 1 >= l.N || b1 + S - 1 < n + g),
+                msg(": halo deeper than the ghosts in ", ax));
+    if (!ranged) return;
+    const bool lo_ok = r0 <= b0 - (S - 1) || g0 + r0 <= 1;
+    const bool hi_ok = r1 >= b1 + (S - 1) || g0 + r1 >= l.N;
+    W3D_REQUIRE(lo_ok && hi_ok, msg(": stage-1 range does not cover the box halo in ", ax));
+    W3D_REQUIRE(r0 >= -g && r1 <= n + g, msg(": real range outside the allocation in ", ax));
+  };
+  axis(b.x0, b.x1, real.x0, real.x1, l.gx0, l.nx, l.xg, true, "x");
+  axis(b.y0, b.y1, real.y0, real.y1, l.gy0, l.ny, l.yg, yz_real, "y");
+  axis(b.z0, b.z1, real.z0, real.z1, l.gz0, l.nz, l.zg, yz_real, "z");
+  return real;
+}
 
 // Error partials per level that a launch_leapfrog_tb over `box` writes: a slot holds either kernel's partials (the
 // pair-tiled pass may split x differently).
 inline int tb_partials(const Layout& l, const LBox& box, const LeapfrogTbTiling& t) {
   if (box.x1 <= box.x0 || box.y1 <= box.y0 || box.z1 <= box.z0) return 0;
-  const int n = tb_round(tb_box_grid(box, t).blocks(), t);
+  const int n = pass_round(tb_box_grid(box, t).blocks(), t);
   return t.p2 && leapfrog_p2_supported(l, box, 2) ? static_cast<int>(imax(n, p2_partials(box, t))) : n;
 }
 
@@ -159,17 +200,18 @@ inline int tb_slot_blocks(const Layout& l, const LBox& full, const LeapfrogTbTil
 
 // Workgroups of ONE pair-tiled launch of t.stages steps over all of a unit's shell boxes (no XCD remap: the boxes'
 // workgroups differ in length), or 0 where the boxes get one launch each:
-//   * fewer than two boxes, more than a launch holds, or a box the pair-tiled pass does not take;
+//   * fewer than two boxes, more than a launch holds, or a box the pair-tiled pass does not run (pass_kernel);
 //   * the shells' tiles alone fill the GPU (a 2048³ block rank's x-slab shell has 961 tiles of 5 planes beside 63
 //     border tiles of 1024 — one grid then runs no faster than three, and measured slower);
 //   * the combined grid does not fit the partial slot of `slot` workgroups. Every box keeps at least its tile count
 //     whatever its work share (p2_launch_grid), so the sum reaches target_blocks + Σ tiles: an interior rank with
 //     11 × 11 tiles at S = 5, target 256, needs 402 workgroups against a slot of 384.
-inline int tb_shells_launch_blocks(const Layout& l, const LBox* boxes, int n, LeapfrogTbTiling t, int slot) {
-  if (n < 2 || n > kP2MaxBoxes || !t.p2) return 0;
+inline int tb_shells_launch_blocks(const Layout& l, const LBox* boxes, int n, LeapfrogTbTiling t, int slot,
+                                   bool analytic_start = false, bool push = false, bool pack = false) {
+  if (n < 2 || n > kP2MaxBoxes) return 0;
   i64 tiles = 0;
   for (int k = 0; k < n; ++k) {
-    if (!leapfrog_p2_supported(l, boxes[k], t.stages)) return 0;
+    if (pass_kernel(l, boxes[k], t.stages, t.p2, analytic_start, push, pack) != PassKernel::kP2) return 0;
     tiles += ceil_div(imax(0, boxes[k].y1 - boxes[k].y0), kTbTile) * ceil_div(imax(0, boxes[k].z1 - boxes[k].z0), kTbTile);
   }
   if (tiles > t.target_blocks) return 0;

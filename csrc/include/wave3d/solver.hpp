@@ -193,16 +193,11 @@ class GpuSolver {
   void unit_shell(int i);
   void unit_exchange_rccl(int i);
   void unit_interior(int i);
-  // What the LDS pass launches of unit u share: the tiling, time factors and check mask of its levels, its slot of
-  // partials (counted in tb_slots_ when a level is checked) and the stage-real ranges.
-  struct TbArgs {
-    LeapfrogTbTiling t;
-    double cts[5] = {0, 0, 0, 0, 0};
-    int mask = 0, slots = 1;
-    Partial* part = nullptr;
-    LBox real;
-  };
-  TbArgs tb_args(const UnitPlan& u);
+  // What the LDS pass launches of unit u share: the buffers, the tiling, time factors and check mask of its levels, its
+  // slot of partials (counted in tb_slots_ when a level is checked) and the stage-real ranges.
+  PassArgs tb_args(const UnitPlan& u);
+  // whether unit u's passes pack the z faces of the exchange that follows it (entry u.depth of pk_host_ / pk_dev_)
+  bool tb_packs(const UnitPlan& u) const { return pk_dev_ != nullptr && u.exchange && pk_host_[u.depth].w == u.depth; }
   void tb_pass(const UnitPlan& u, const LBox& box, int phase, hipStream_t st = nullptr);  // one k_leapfrog_tb launch
   // the unit's shell boxes in ONE pair-tiled launch when that applies (returns false: launch them one by one)
   bool tb_pass_boxes(const UnitPlan& u, const std::vector<LBox>& boxes, int phase, hipStream_t st);

@@ -7,6 +7,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <tuple>
 
 #include "wave3d/capture_guard.hpp"
@@ -40,6 +41,29 @@ T* dptr(std::uintptr_t p) {
   return reinterpret_cast<T*>(p);
 }
 hipStream_t sptr(std::uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The flat argument list that the Python pass launchers (gpu_leapfrog_tb, gpu_leapfrog_p2_boxes) share, in their
+// order, as the launchers' struct.
+PassArgs py_pass_args(std::uintptr_t prev, std::uintptr_t cur, std::uintptr_t out1, std::uintptr_t out2,
+                      std::uintptr_t s, const std::vector<double>& ct, int check_mask, std::uintptr_t partials,
+                      const LeapfrogTbTiling& t, const LBox& real, bool analytic_start, int level_stride,
+                      int grid_blocks) {
+  PassArgs a;
+  a.prev = dptr<const double>(prev);
+  a.cur = dptr<const double>(cur);
+  a.out1 = dptr<double>(out1);
+  a.out2 = dptr<double>(out2);
+  a.d_s = dptr<const double>(s) + 1;
+  std::copy_n(ct.begin(), std::min<size_t>(ct.size(), 5), a.ct);
+  a.check_mask = check_mask;
+  a.partials = dptr<Partial>(partials);
+  a.level_stride = level_stride;
+  a.grid_blocks = grid_blocks;
+  a.tiling = t;
+  a.real = real;
+  a.analytic_start = analytic_start;
+  return a;
+}
 
 py::dict result_dict(const RunResult& r) {
   py::dict d;
@@ -523,39 +547,34 @@ PYBIND11_MODULE(_C, m) {
   // [low z u^{n+S}, low z u^{n+S−1}, high z u^{n+S}, high z u^{n+S−1}] (0: no such part), pack_w: the band width
   m.def("gpu_leapfrog_tb",
         [](const Layout& l, const Coeffs& c, std::uintptr_t prev, std::uintptr_t cur, std::uintptr_t out1,
-           std::uintptr_t out2, const LBox& box, std::uintptr_t s, std::vector<double> ct, int check_mask,
+           std::uintptr_t out2, const LBox& box, std::uintptr_t s, const std::vector<double>& ct, int check_mask,
            std::uintptr_t partials, const LeapfrogTbTiling& t, std::uintptr_t stream, const LBox& real,
            bool analytic_start, int level_stride, int grid_blocks, const std::vector<std::uintptr_t>& pack_zf,
            int pack_w) {
-          ct.resize(5, 0.0);
-          if (pack_zf.empty()) {
-            launch_leapfrog_tb(l, c, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
-                               dptr<double>(out2), box, dptr<const double>(s) + 1, ct.data(), check_mask,
-                               dptr<Partial>(partials), t, sptr(stream), real, analytic_start, level_stride,
-                               grid_blocks);
-            return;
-          }
-          W3D_REQUIRE(pack_zf.size() == 4, "gpu_leapfrog_tb: pack_zf takes four pointers");
+          PassArgs a = py_pass_args(prev, cur, out1, out2, s, ct, check_mask, partials, t, real, analytic_start,
+                                    level_stride, grid_blocks);
           TbPack pk;
-          for (int side = 0; side < 2; ++side)
-            for (int f = 0; f < 2; ++f) pk.zf[side][f] = dptr<double>(pack_zf[static_cast<size_t>(2 * side + f)]);
-          pk.w = pack_w;
-          pk.ny = static_cast<int>(l.ny);
-          pk.nz = static_cast<int>(l.nz);
           TbPack* dev = nullptr;
-          W3D_HIP(hipMalloc(&dev, sizeof(TbPack)));
+          if (!pack_zf.empty()) {
+            W3D_REQUIRE(pack_zf.size() == 4, "gpu_leapfrog_tb: pack_zf takes four pointers");
+            for (int side = 0; side < 2; ++side)
+              for (int f = 0; f < 2; ++f) pk.zf[side][f] = dptr<double>(pack_zf[static_cast<size_t>(2 * side + f)]);
+            pk.w = pack_w;
+            pk.ny = static_cast<int>(l.ny);
+            pk.nz = static_cast<int>(l.nz);
+            W3D_HIP(hipMalloc(&dev, sizeof(TbPack)));
+            a.pack = &pk;
+            a.pack_dev = dev;
+          }
           try {
-            W3D_HIP(hipMemcpy(dev, &pk, sizeof(TbPack), hipMemcpyHostToDevice));
-            launch_leapfrog_tb(l, c, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
-                               dptr<double>(out2), box, dptr<const double>(s) + 1, ct.data(), check_mask,
-                               dptr<Partial>(partials), t, sptr(stream), real, analytic_start, level_stride,
-                               grid_blocks, nullptr, nullptr, &pk, dev);
-            W3D_HIP(hipStreamSynchronize(sptr(stream)));  // (the kernel reads the parameters from `dev`)
+            if (dev) W3D_HIP(hipMemcpy(dev, &pk, sizeof(TbPack), hipMemcpyHostToDevice));
+            launch_leapfrog_tb(l, c, box, a, sptr(stream));
+            if (dev) W3D_HIP(hipStreamSynchronize(sptr(stream)));  // (the kernel reads the parameters from `dev`)
           } catch (...) {
             (void)hipFree(dev);
             throw;
           }
-          W3D_HIP(hipFree(dev));
+          if (dev) W3D_HIP(hipFree(dev));
         },
         py::arg("layout"), py::arg("coeffs"), py::arg("prev"), py::arg("cur"), py::arg("out1"), py::arg("out2"),
         py::arg("box"), py::arg("s"), py::arg("ct"), py::arg("check_mask"), py::arg("partials"), py::arg("tiling"),
@@ -565,14 +584,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("gpu_leapfrog_p2_partials", &leapfrog_p2_partials);
   m.def("gpu_leapfrog_p2_boxes",
         [](const Layout& l, const Coeffs& c, std::uintptr_t prev, std::uintptr_t cur, std::uintptr_t out1,
-           std::uintptr_t out2, const std::vector<LBox>& boxes, std::uintptr_t s, std::vector<double> ct,
+           std::uintptr_t out2, const std::vector<LBox>& boxes, std::uintptr_t s, const std::vector<double>& ct,
            int check_mask, std::uintptr_t partials, const LeapfrogTbTiling& t, std::uintptr_t stream, const LBox& real,
            bool analytic_start, int level_stride, int grid_blocks) {
-          ct.resize(5, 0.0);
-          launch_leapfrog_p2_boxes(l, c, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
-                                   dptr<double>(out2), boxes.data(), static_cast<int>(boxes.size()),
-                                   dptr<const double>(s) + 1, ct.data(), check_mask, dptr<Partial>(partials), t,
-                                   sptr(stream), real, analytic_start, level_stride, grid_blocks);
+          PassArgs a = py_pass_args(prev, cur, out1, out2, s, ct, check_mask, partials, t, real, analytic_start,
+                                    level_stride, grid_blocks);
+          launch_leapfrog_p2_boxes(l, c, boxes.data(), static_cast<int>(boxes.size()), a, sptr(stream));
         },
         py::arg("layout"), py::arg("coeffs"), py::arg("prev"), py::arg("cur"), py::arg("out1"), py::arg("out2"),
         py::arg("boxes"), py::arg("s"), py::arg("ct"), py::arg("check_mask"), py::arg("partials"), py::arg("tiling"),

@@ -41,27 +41,12 @@ using namespace p2k;
 
 namespace {
 
-struct P2Plan {
-  P2Params prm{};
-  int nblocks = 0;
-};
-
-// the checks a box must pass; its grid (tiles × x chunks, first workgroup) is g (pass_grid.hpp p2_launch_grid)
-void p2_box(const Layout& l, const LBox& b, const LeapfrogTbTiling& t, const LBox& real, const PassBoxGrid& g, P2Box& bx) {
-  const int S = t.stages;
-  W3D_REQUIRE(leapfrog_p2_supported(l, b, S), "leapfrog_p2: the box must lie in the rank's y/z range on whole pairs");
-  // x: u^{n+k} (k < S) is read up to S−k planes beyond the box (real there, or beyond the global boundary); u^n is
-  // read S planes beyond, within the allocation unless beyond the global boundary
-  const bool lo_ok = real.x0 <= b.x0 - (S - 1) || l.gx0 + real.x0 <= 1;
-  const bool hi_ok = real.x1 >= b.x1 + (S - 1) || l.gx0 + real.x1 >= l.N;
-  W3D_REQUIRE(lo_ok && hi_ok, "leapfrog_p2: stage-1 range does not cover the box halo in x");
-  W3D_REQUIRE(l.gx0 + b.x0 - S <= 0 || b.x0 - S >= -l.xg, "leapfrog_p2: halo deeper than the ghosts in x");
-  W3D_REQUIRE(l.gx0 + b.x1 + S - 1 >= l.N || b.x1 + S - 1 < l.nx + l.xg, "leapfrog_p2: halo deeper than the ghosts in x");
-  // y / z (3-D block ranks): u^n is read S nodes beyond the box, within the ghosts unless beyond the global boundary
-  W3D_REQUIRE(l.gy0 + b.y0 - S <= 0 || b.y0 - S >= -l.yg, "leapfrog_p2: halo deeper than the ghosts in y");
-  W3D_REQUIRE(l.gy0 + b.y1 + S - 1 >= l.N || b.y1 + S - 1 < l.ny + l.yg, "leapfrog_p2: halo deeper than the ghosts in y");
-  W3D_REQUIRE(l.gz0 + b.z0 - S <= 0 || b.z0 - S >= -l.zg, "leapfrog_p2: halo deeper than the ghosts in z");
-  W3D_REQUIRE(l.gz0 + b.z1 + S - 1 >= l.N || b.z1 + S - 1 < l.nz + l.zg, "leapfrog_p2: halo deeper than the ghosts in z");
+// the checks a box must pass (returns `real` resolved); its grid (tiles × x chunks, first workgroup) is g (pass_grid.hpp
+// p2_launch_grid)
+LBox p2_box(const Layout& l, const LBox& b, const LeapfrogTbTiling& t, LBox real, const PassBoxGrid& g, P2Box& bx) {
+  W3D_REQUIRE(leapfrog_p2_supported(l, b, t.stages),
+              "leapfrog_p2: the box must lie in the rank's y/z range on whole pairs");
+  real = pass_box_check(l, b, t.stages, real, "leapfrog_p2", false);
   bx.x0 = static_cast<int>(b.x0);
   bx.x1 = static_cast<int>(b.x1);
   bx.y0 = static_cast<int>(b.y0);
@@ -79,32 +64,24 @@ void p2_box(const Layout& l, const LBox& b, const LeapfrogTbTiling& t, const LBo
   bx.ntz = g.ntz;
   bx.xlen = g.xlen;
   bx.nxc = g.nxc;
+  return real;
 }
 
 // A launch over n boxes (n ≤ kP2Boxes): one grid, box k from workgroup blk0_k on; the block counts are the host-side
-// arithmetic of pass_grid.hpp (p2_launch_grid), which also sizes the partial slots.
-P2Plan make_plan_p2(const Layout& l, const LBox* boxes, int n, const LeapfrogTbTiling& t, LBox real, bool init) {
+// arithmetic of pass_grid.hpp (p2_launch_grid), which also sizes the partial slots. nblocks = 0: nothing to launch.
+P2Params make_plan_p2(const Layout& l, const LBox* boxes, int n, const LeapfrogTbTiling& t, LBox real, bool init) {
   const int S = t.stages;
   W3D_REQUIRE(S >= 2 && S <= 5, "leapfrog_p2: stages must be 2..5");
   W3D_REQUIRE(!init || S <= 4, "leapfrog_p2: the analytic-start pass takes at most 4 steps");
   W3D_REQUIRE(n >= 1 && n <= kP2Boxes, "leapfrog_p2: too many boxes for one launch");
   W3D_REQUIRE(l.plane < (i64{1} << 27), "leapfrog_p2: plane too large for 32-bit buffer offsets");
-  const LBox full = compute_box(l);
-  if (real.x0 > real.x1) {
-    real.x0 = full.x0;
-    real.x1 = full.x1;
-  }
-  W3D_REQUIRE(real.x0 >= -l.xg && real.x1 <= l.nx + l.xg, "leapfrog_p2: real range outside the allocation in x");
-  P2Plan pl;
-  P2Params& p = pl.prm;
+  P2Params p{};
   p.plane = l.plane;
   p.pitch = static_cast<int>(l.pitch);
   p.ya = static_cast<int>(l.yg);
   p.za = static_cast<int>(l.zg + l.zs);
   p.ay0 = static_cast<int>(-l.yg);
   p.ay1 = static_cast<int>(l.ny + l.yg);
-  p.sx0 = static_cast<int>(real.x0);
-  p.sx1 = static_cast<int>(real.x1);
   p.ax0 = static_cast<int>(-l.xg);
   p.ax1 = static_cast<int>(l.nx + l.xg);
   p.N = static_cast<int>(l.N);
@@ -115,15 +92,17 @@ P2Plan make_plan_p2(const Layout& l, const LBox* boxes, int n, const LeapfrogTbT
   p.nbox = n;
   p.chunked = gr.chunked ? 1 : 0;
   p.xlen_max = gr.xlen_max;
-  for (int k = 0; k < n; ++k) p2_box(l, boxes[k], t, real, gr.box[k], p.box[k]);
+  LBox r = real;  // (the same resolved range from every box)
+  for (int k = 0; k < n; ++k) r = p2_box(l, boxes[k], t, real, gr.box[k], p.box[k]);
+  p.sx0 = static_cast<int>(r.x0);
+  p.sx1 = static_cast<int>(r.x1);
   const int blk = gr.nactive;
   p.nactive = blk;
-  if (blk == 0) return pl;
-  pl.nblocks = gr.nblocks;
-  p.nblocks = pl.nblocks;
+  if (blk == 0) return p;
+  p.nblocks = gr.nblocks;
   p.xcd_remap = t.xcd_remap ? 1 : 0;
-  p.xper = pl.nblocks / 8;
-  return pl;
+  p.xper = p.nblocks / 8;
+  return p;
 }
 
 #ifdef W3D_EXPERIMENT_WGTIME
@@ -215,64 +194,35 @@ void leapfrog_p2_prepare() {
   prepare_p2_box_s5();
 }
 
-void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
-                              double* out2, const LBox* boxes, int nbox, const double* d_s, const double* ct,
-                              int check_mask, Partial* partials, const LeapfrogTbTiling& t, hipStream_t stream,
-                              const LBox& real, bool analytic_start, int level_stride, int grid_blocks) {
-  W3D_REQUIRE(out1 != out2 && (analytic_start || (prev != out1 && prev != out2 && cur != out1 && cur != out2)),
-              "leapfrog_p2 needs four distinct buffers");
-  P2Plan pl = make_plan_p2(l, boxes, nbox, t, real, analytic_start);
-  if (pl.nblocks == 0) return;
-  P2Params& p = pl.prm;
-  if (grid_blocks > 0) {
-    W3D_REQUIRE(grid_blocks >= pl.nblocks && (!t.xcd_remap || grid_blocks % 8 == 0), "leapfrog_p2: bad grid_blocks");
-    // (the padded grid's extra blocks get no tile: xper stays the active blocks' per-XCD share, else the remap would
-    // hand every tile to the first XCDs — measured: a slab rank's 256 tiles on 4 of 8 XCDs, passes 2.2x slower)
-    pl.nblocks = p.nblocks = grid_blocks;
+void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const LBox* boxes, int nbox, const PassArgs& a,
+                              hipStream_t stream) {
+  const LeapfrogTbTiling& t = a.tiling;
+  P2Params p = make_plan_p2(l, boxes, nbox, t, a.real, a.analytic_start);
+  if (!fill_pass_params(p, l, c, a, "leapfrog_p2")) return;
+  if (a.analytic_start) {  // (the analytic start reads neither: any valid buffer)
+    p.prev = p.out1;
+    p.cur = p.out2;
   }
-  const i64 kb = (l.xg - 1) * l.plane;  // x base only: in-plane offsets are plane-relative
-  p.prev = analytic_start ? out1 + kb : prev + kb;  // (the analytic start reads neither: any valid buffer)
-  p.cur = analytic_start ? out2 + kb : cur + kb;
-  p.out1 = out1 + kb;
-  p.out2 = out2 + kb;
-  p.s = d_s;
-  p.tau2 = c.lam;
-  p.half_tau2 = c.half_lam;
-  p.ry = c.ry;
-  p.rz = c.rz;
-  p.check_mask = partials != nullptr ? (check_mask & ((1 << t.stages) - 1)) : 0;
-  p.partials = p.check_mask != 0 ? partials : nullptr;
-  W3D_REQUIRE(level_stride == 0 || level_stride >= pl.nblocks, "leapfrog_p2: level stride below the block count");
-  p.lstride = level_stride > 0 ? level_stride : pl.nblocks;
-  for (int k = 0; k < 5; ++k) p.ct[k] = (ct != nullptr && k < t.stages) ? ct[k] : 0.0;
 #ifdef W3D_EXPERIMENT_WGTIME
-  p.wgtime = wgtime_slot(pl.nblocks, t.stages, analytic_start);
+  p.wgtime = wgtime_slot(p.nblocks, t.stages, a.analytic_start);
 #endif
   if (c.box) {  // (a rectangular box: the BOX instantiations; a cube launches exactly what it always did)
     switch (t.stages) {
-      case 2: launch_p2_box_s2(p, pl.nblocks, analytic_start, stream); break;
-      case 3: launch_p2_box_s3(p, pl.nblocks, analytic_start, stream); break;
-      case 4: launch_p2_box_s4(p, pl.nblocks, analytic_start, stream); break;
-      default: launch_p2_box_s5(p, pl.nblocks, analytic_start, stream); break;
+      case 2: launch_p2_box_s2(p, p.nblocks, a.analytic_start, stream); break;
+      case 3: launch_p2_box_s3(p, p.nblocks, a.analytic_start, stream); break;
+      case 4: launch_p2_box_s4(p, p.nblocks, a.analytic_start, stream); break;
+      default: launch_p2_box_s5(p, p.nblocks, a.analytic_start, stream); break;
     }
   } else {
     switch (t.stages) {
-      case 2: launch_p2_s2(p, pl.nblocks, analytic_start, stream); break;
-      case 3: launch_p2_s3(p, pl.nblocks, analytic_start, stream); break;
-      case 4: launch_p2_s4(p, pl.nblocks, analytic_start, stream); break;
-      default: launch_p2_s5(p, pl.nblocks, analytic_start, stream); break;
+      case 2: launch_p2_s2(p, p.nblocks, a.analytic_start, stream); break;
+      case 3: launch_p2_s3(p, p.nblocks, a.analytic_start, stream); break;
+      case 4: launch_p2_s4(p, p.nblocks, a.analytic_start, stream); break;
+      default: launch_p2_s5(p, p.nblocks, a.analytic_start, stream); break;
     }
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) fail(std::string("leapfrog_p2 launch: ") + hipGetErrorString(e));
-}
-
-void launch_leapfrog_p2(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
-                        double* out2, const LBox& box, const double* d_s, const double* ct, int check_mask,
-                        Partial* partials, const LeapfrogTbTiling& t, hipStream_t stream, const LBox& real,
-                        bool analytic_start, int level_stride, int grid_blocks) {
-  launch_leapfrog_p2_boxes(l, c, prev, cur, out1, out2, &box, 1, d_s, ct, check_mask, partials, t, stream, real,
-                           analytic_start, level_stride, grid_blocks);
 }
 
 }  // namespace wave3d

@@ -81,82 +81,53 @@ int leapfrog_tb_partials(const Layout& l, const LBox& box, const LeapfrogTbTilin
   return tb_partials(l, box, t);
 }
 
-void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
-                        double* out2, const LBox& box, const double* d_s, const double* ct, int check_mask,
-                        Partial* partials, const LeapfrogTbTiling& t, hipStream_t stream, const LBox& real,
-                        bool analytic_start, int level_stride, int grid_blocks, const TbPush* push,
-                        const TbPush* push_dev, const TbPack* pack, const TbPack* pack_dev) {
-  W3D_REQUIRE(out1 != out2 && (analytic_start || (prev != out1 && prev != out2 && cur != out1 && cur != out2)),
-              "leapfrog_tb needs four distinct buffers");
-  if (t.p2 && (push == nullptr || !push->on) && pack == nullptr && leapfrog_p2_supported(l, box, t.stages) &&
-      (!analytic_start || t.stages <= 4)) {
-    launch_leapfrog_p2(l, c, prev, cur, out1, out2, box, d_s, ct, check_mask, partials, t, stream, real,
-                       analytic_start, level_stride, grid_blocks);
+void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const LBox& box, const PassArgs& a, hipStream_t stream) {
+  const LeapfrogTbTiling& t = a.tiling;
+  const TbPush* push = a.push != nullptr && a.push->on ? a.push : nullptr;
+  if (pass_kernel(l, box, t.stages, t.p2, a.analytic_start, push != nullptr, a.pack != nullptr) == PassKernel::kP2) {
+    launch_leapfrog_p2_boxes(l, c, &box, 1, a, stream);
     return;
   }
   W3D_REQUIRE(t.stages <= 4, "leapfrog_tb: 5-step passes need the pair-tiled kernel (tiling.p2)");
   W3D_REQUIRE(t.ghost_x1 == 0, "leapfrog_tb: ghost-plane stores (tiling.ghost_x1) need the pair-tiled kernel");
-  TbPlan pl = make_plan_tb(l, box, t, real);
-  if (pl.nblocks == 0) return;
-  TbParams& p = pl.prm;
-  if (push != nullptr && push->on) {
+  TbParams p = make_plan_tb(l, box, t, a.real);
+  if (!fill_pass_params(p, l, c, a, "leapfrog_tb")) return;
+  if (a.grid_blocks > 0) p.bby = p.bbz = 0;  // (a padded grid's extra workgroups have no tile)
+  p.ihx2 = c.ihx2;
+  p.ihy2 = c.ihy2;
+  p.ihz2 = c.ihz2;
+  if (push != nullptr) {
     // the staging holds T planes per side in this rank's plane geometry; the forwarded planes are this rank's own
     W3D_REQUIRE(push->T == l.xg && push->nx == l.nx && t.stages <= push->T && l.yg == 1 && l.zg == 1,
                 "leapfrog_tb push: slab ranks with T-deep x ghosts only");
     W3D_REQUIRE(push->T >= 2 && l.nx >= push->T, "leapfrog_tb push: a rank needs at least T planes");
-    W3D_REQUIRE(push_dev != nullptr, "leapfrog_tb push: the pass parameters must be in device memory");
-    p.push = push_dev;
+    W3D_REQUIRE(a.push_dev != nullptr, "leapfrog_tb push: the pass parameters must be in device memory");
+    W3D_REQUIRE(push->signal_epoch == 0 || push->done_target % static_cast<unsigned>(p.nblocks) == 0,
+                "leapfrog_tb push: done_target must be a multiple of the grid");  // (every pass of a solve: one full grid)
+    W3D_REQUIRE(!c.box, "leapfrog_tb push: the push transport has no rectangular-box kernels (cube domains only; use "
+                        "another transport for --box)");
+    p.push = a.push_dev;
     p.pnx = push->nx;
     p.pT = push->T;
     p.ptag = push->tag;
     p.pacq = push->acquire;
   }
-  if (pack != nullptr) {  // fused z-face pack: the host copy gives the band limits, the kernel reads the rest on use
-    W3D_REQUIRE(pack_dev != nullptr && pack->w >= 2 && pack->w <= kTile && pack->ny == l.ny && pack->nz == l.nz,
+  if (const TbPack* pack = a.pack) {  // fused z-face pack: the host copy gives the band limits, the kernel reads the rest on use
+    W3D_REQUIRE(a.pack_dev != nullptr && pack->w >= 2 && pack->w <= kTile && pack->ny == l.ny && pack->nz == l.nz,
                 "leapfrog_tb pack: bad parameters");
-    p.pk = pack_dev;
+    p.pk = a.pack_dev;
     p.pkza = pack->zf[0][0] ? pack->w : 0;
     p.pkzb = pack->zf[1][0] ? pack->nz - pack->w : pack->nz;
   }
-  // a padded grid (several launches sharing one level's partial slots, each of grid_blocks entries): the extra
-  // workgroups have no tile and write (0, 0) partials, so every slot entry a reduction reads is written
-  if (grid_blocks > 0) {
-    W3D_REQUIRE(grid_blocks >= pl.nblocks && (!t.xcd_remap || grid_blocks % 8 == 0), "leapfrog_tb: bad grid_blocks");
-    pl.nblocks = p.nblocks = grid_blocks;
-    p.bby = p.bbz = 0;
-  }
-  const i64 kb = (l.xg - 1) * l.plane;  // x base only: in-plane offsets are plane-relative (non-negative)
-  p.prev = analytic_start ? nullptr : prev + kb;
-  p.cur = analytic_start ? nullptr : cur + kb;
-  p.out1 = out1 + kb;
-  p.out2 = out2 + kb;
-  p.s = d_s;
-  p.ihx2 = c.ihx2;
-  p.ihy2 = c.ihy2;
-  p.ihz2 = c.ihz2;
-  p.tau2 = c.lam;  // τ²/h² and τ²/(2h²): the coefficients of d2sum
-  p.half_tau2 = c.half_lam;
-  p.ry = c.ry;
-  p.rz = c.rz;
-  p.check_mask = partials != nullptr ? (check_mask & ((1 << t.stages) - 1)) : 0;
-  p.partials = p.check_mask != 0 ? partials : nullptr;
-  W3D_REQUIRE(level_stride == 0 || level_stride >= pl.nblocks, "leapfrog_tb: level stride below the block count");
-  p.lstride = level_stride > 0 ? level_stride : pl.nblocks;
-  for (int k = 0; k < 4; ++k) p.ct[k] = (ct != nullptr && k < t.stages) ? ct[k] : 0.0;
-  if (push != nullptr && push->on && push->signal_epoch != 0)  // (every pass of a solve: one full grid)
-    W3D_REQUIRE(push->done_target % static_cast<unsigned>(pl.nblocks) == 0,
-                "leapfrog_tb push: done_target must be a multiple of the grid");
-  if (push != nullptr && push->on) {
-    W3D_REQUIRE(!c.box, "leapfrog_tb push: the push transport has no rectangular-box kernels (cube domains only; use "
-                        "another transport for --box)");
-    launch_push(p, pl.nblocks, t.stages, analytic_start, t.init_threads, stream);
+  if (push != nullptr) {
+    launch_push(p, p.nblocks, t.stages, a.analytic_start, t.init_threads, stream);
   } else if (c.box) {
-    launch_box(p, pl.nblocks, t, analytic_start, stream);
+    launch_box(p, p.nblocks, t, a.analytic_start, stream);
   } else {
     switch (t.stages) {
-      case 2: launch_s<2, false>(p, pl.nblocks, t, analytic_start, stream); break;
-      case 3: launch_s<3, false>(p, pl.nblocks, t, analytic_start, stream); break;
-      default: launch_s<4, false>(p, pl.nblocks, t, analytic_start, stream); break;
+      case 2: launch_s<2, false>(p, p.nblocks, t, a.analytic_start, stream); break;
+      case 3: launch_s<3, false>(p, p.nblocks, t, a.analytic_start, stream); break;
+      default: launch_s<4, false>(p, p.nblocks, t, a.analytic_start, stream); break;
     }
   }
   const hipError_t e = hipGetLastError();

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 
+#include "wave3d/pass_grid.hpp"
+
 namespace wave3d {
 
 namespace {
@@ -10,7 +12,8 @@ namespace {
 // 5-step passes exist only in the pair-tiled kernel (k_leapfrog_p2): temporal 5 becomes 4 when that kernel is off
 // (tb or tiling_tb.p2 unset), and on several ranks unless they run deep-tb on a transport other than push (whose
 // forwarding stores are k_leapfrog_tb's, S ≤ 4). (3-D blocks, overlapped or not, keep 5: the overlapped schedule's
-// shell and interior boxes are cut on whole pairs, cpu.hpp deep_split.)
+// shell and interior boxes are cut on whole pairs, cpu.hpp deep_split.) These are consequences of pass_kernel
+// (pass_grid.hpp), decided here before a layout exists to ask it about.
 int clamp_temporal(const SolverOptions& o, int world, bool deep_tb) {
   const bool five = o.tb && o.tiling_tb.p2 && (world == 1 || (deep_tb && !o.push));
   return o.temporal == 5 && !five ? 4 : o.temporal;
@@ -83,7 +86,8 @@ RankSchedule make_rank_schedule(const Problem& prob, const SolverOptions& opt, i
   }
   s.block_tb = s.mode == Mode::kDeepTb && !slab;
   s.opt.temporal = clamp_temporal(opt, world, s.mode == Mode::kDeepTb);
-  // (the fused z-face pack lives in k_leapfrog_tb: with the pair-tiled pass the pack kernel packs the z faces too)
+  // (the fused z-face pack lives in k_leapfrog_tb — a launch with a pack never goes to the pair-tiled pass, pass_kernel
+  // in pass_grid.hpp — so with that pass asked for, the pack kernel packs the z faces too)
   if (s.block_tb && opt.tiling_tb.p2) s.opt.fused_pack = false;
   if (opt.push && world > 1) {
     W3D_REQUIRE(s.mode == Mode::kDeepTb && !s.block_tb,
@@ -169,6 +173,13 @@ RankSchedule make_rank_schedule(const Problem& prob, const SolverOptions& opt, i
 
 namespace {
 
+// Whether the pair-tiled kernel runs the passes of `stages` steps of this rank (pass_kernel, asked about the whole
+// compute box: deep_split cuts the overlapped schedule's sub-boxes on whole pairs, so they get the same answer).
+bool runs_p2(const RankSchedule& s, int stages, bool analytic) {
+  return pass_kernel(s.lay, s.full, stages, s.opt.tiling_tb.p2, analytic, s.push, s.block_tb && s.opt.fused_pack) ==
+         PassKernel::kP2;
+}
+
 // Split the steps start_n..K into passes of 1..temporal steps minimising the summed cost: µs per step of a pass of s
 // steps with every 2nd level checked, measured at 512³ (tools/tune_leapfrog.py --tb); the analytic first pass reads
 // nothing but computes u⁰, u¹ (compute-bound). Slab and block ranks (deep-tb) take passes of ≥ 2 steps only: every
@@ -180,8 +191,7 @@ void plan_passes(const RankSchedule& s, int n, bool analytic, std::vector<UnitPl
   // the pair-tiled passes (k_leapfrog_p2, one rank): µs per step at 512³ (profiles/r5/)
   static const double kStepCostP2[6] = {0.0, 610.0, 430.0, 290.0, 225.0, 180.0};
   static const double kAnalyticCostP2[6] = {0.0, 1e9, 300.0, 200.0, 135.0, 1e9};
-  // (slab ranks and 3-D block ranks too: their shell / interior boxes are cut on whole pairs)
-  const bool p2 = s.opt.tiling_tb.p2 && !s.push && leapfrog_p2_supported(s.lay, s.full, 2);
+  const bool p2 = runs_p2(s, 2, false);
   const double* kStepCost = p2 ? kStepCostP2 : kStepCostTb;
   const double* kAnalyticCost = p2 ? kAnalyticCostP2 : kAnalyticCostTb;
   const int K = s.prob.K, rem = K - n, smax = s.opt.temporal, smin = s.mode == Mode::kDeepTb ? 2 : 1;
@@ -274,8 +284,7 @@ std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analyt
     u.exchange = s.halo.any() && !s.push && (s.post_exchange() ? i + 1 < nu : i > 0);
     if (!u.exchange) continue;
     if (tb) u.depth = units[static_cast<size_t>(i) + 1].steps;
-    if (tb && s.opt.ghost_store && !s.block_tb && s.opt.tiling_tb.p2 && !(u.analytic && u.steps > 4) &&
-        leapfrog_p2_supported(s.lay, s.full, u.steps))
+    if (tb && s.opt.ghost_store && !s.block_tb && runs_p2(s, u.steps, u.analytic))
       for (const Face& f : s.halo.faces)
         if (f.axis == 0) u.ghost_bits |= 1 << f.side;
     plan_msgs(s, u);

@@ -671,19 +671,28 @@ void GpuSolver::unit_exchange_rccl(int i) {
   if (xs != s0_) capture::record(ev_halo_, xs);
 }
 
-GpuSolver::TbArgs GpuSolver::tb_args(const UnitPlan& u) {
-  TbArgs a;
-  a.t = sch_.opt.tiling_tb;
-  a.t.stages = u.steps;
-  a.t.ghost_x1 = u.ghost_bits;
+PassArgs GpuSolver::tb_args(const UnitPlan& u) {
+  PassArgs a;
+  a.prev = u_[old_];
+  a.cur = u_[cur_];
+  a.out1 = u_[uf_[0]];
+  a.out2 = u_[uf_[1]];
+  a.d_s = d_s_ + 1;
+  a.tiling = sch_.opt.tiling_tb;
+  a.tiling.stages = u.steps;
+  a.tiling.ghost_x1 = u.ghost_bits;
   for (int k = 1; k <= u.steps; ++k) {
-    a.cts[k - 1] = ct_[static_cast<size_t>(u.n + k)];
-    if (is_check_[static_cast<size_t>(u.n + k)]) a.mask |= 1 << (k - 1);
+    a.ct[k - 1] = ct_[static_cast<size_t>(u.n + k)];
+    if (is_check_[static_cast<size_t>(u.n + k)]) a.check_mask |= 1 << (k - 1);
   }
-  a.slots = sch_.mode == Mode::kDeepTb ? kTbSlots : 1;
-  W3D_REQUIRE(tb_slots_ < a.slots, "leapfrog_tb: too many launches in one unit");
-  if (a.mask) a.part = tb_partials_ + tb_region_ * (kTbLevels * a.slots * n_tb_) + tb_slots_++ * n_tb_;
+  const int slots = sch_.mode == Mode::kDeepTb ? kTbSlots : 1;
+  W3D_REQUIRE(tb_slots_ < slots, "leapfrog_tb: too many launches in one unit");
+  if (a.check_mask) a.partials = tb_partials_ + tb_region_ * (kTbLevels * slots * n_tb_) + tb_slots_++ * n_tb_;
+  // (every launch fills its whole slot of n_tb_ partials: shell and interior boxes may have fewer x chunks)
+  a.level_stride = slots * n_tb_;
+  a.grid_blocks = n_tb_;
   a.real = sch_.mode == Mode::kDeepTb ? sch_.sreal : tb_default_real();
+  a.analytic_start = u.analytic;
   return a;
 }
 
@@ -692,47 +701,38 @@ GpuSolver::TbArgs GpuSolver::tb_args(const UnitPlan& u) {
 // the interior), reduced together after the interior.
 void GpuSolver::tb_pass(const UnitPlan& u, const LBox& box, int phase, hipStream_t st) {
   if (st == nullptr) st = s0_;
-  const TbArgs a = tb_args(u);
+  PassArgs a = tb_args(u);
   // push transport: this pass's parameters (make_push) from the table phase_init uploaded; the command-processor
   // waits (push_cp_wait) are stream operations issued here, before the launch
-  const TbPush* qh = nullptr;
-  const TbPush* qd = nullptr;
   if (sch_.push) {
-    const int j = cur_unit_ + 1;
-    qh = push_tab_ + (j - 1);
-    qd = push_dev_ + (j - 1);
+    a.push = push_tab_ + cur_unit_;
+    a.push_dev = push_dev_ + cur_unit_;
     if (sch_.opt.push_cp_wait)
       for (int side = 0; side < 2; ++side)
-        if (qh->wait_side[side] && qh->cp_wait > 0)
-          W3D_HIP(hipStreamWaitValue32(s0_, flags_ + side, qh->cp_wait, hipStreamWaitValueGte, 0xFFFFFFFFu));
+        if (a.push->wait_side[side] && a.push->cp_wait > 0)
+          W3D_HIP(hipStreamWaitValue32(s0_, flags_ + side, a.push->cp_wait, hipStreamWaitValueGte, 0xFFFFFFFFu));
   }
-  // fused z-face pack of the exchange that follows this unit
-  const bool pk = pk_dev_ != nullptr && u.exchange && pk_host_[u.depth].w == u.depth;
-  timed(phase, st, [&] {
-    // (every launch fills its whole slot of n_tb_ partials: shell and interior boxes may have fewer x chunks)
-    launch_leapfrog_tb(sch_.lay, coef_, u_[old_], u_[cur_], u_[uf_[0]], u_[uf_[1]], box, d_s_ + 1, a.cts, a.mask, a.part,
-                       a.t, st, a.real, u.analytic, a.slots * n_tb_, n_tb_, qh, qd, pk ? &pk_host_[u.depth] : nullptr,
-                       pk ? pk_dev_ + u.depth : nullptr);
-  });
+  if (tb_packs(u)) {
+    a.pack = &pk_host_[u.depth];
+    a.pack_dev = pk_dev_ + u.depth;
+  }
+  timed(phase, st, [&] { launch_leapfrog_tb(sch_.lay, coef_, box, a, st); });
 }
 
 bool GpuSolver::tb_pass_boxes(const UnitPlan& u, const std::vector<LBox>& boxes, int phase, hipStream_t st) {
-  if (boxes.size() < 2 || boxes.size() > static_cast<size_t>(kP2MaxBoxes) || !sch_.opt.tiling_tb.p2 || sch_.push ||
-      (pk_dev_ != nullptr && pk_host_[u.depth].w == u.depth) || (u.analytic && u.steps > 4))
-    return false;
-  // (only where the shells' tiles alone do not fill the GPU and the combined grid fits the partial slot: pass_grid.hpp;
-  // otherwise one launch per box, each of which fits)
+  // (only where the pair-tiled pass runs every box, the shells' tiles alone do not fill the GPU and the combined grid
+  // fits the partial slot: pass_grid.hpp; otherwise one launch per box, each of which fits)
   LeapfrogTbTiling ts = sch_.opt.tiling_tb;
   ts.stages = u.steps;
-  if (tb_shells_launch_blocks(sch_.lay, boxes.data(), static_cast<int>(boxes.size()), ts, n_tb_) == 0) return false;
-  TbArgs a = tb_args(u);
+  if (tb_shells_launch_blocks(sch_.lay, boxes.data(), static_cast<int>(boxes.size()), ts, n_tb_, u.analytic, sch_.push,
+                              tb_packs(u)) == 0)
+    return false;
+  PassArgs a = tb_args(u);
   // (no XCD remap: the boxes' workgroups differ in length, and a contiguous logical range per XCD put the long ones
   // on a few XCDs; dispatch order deals consecutive workgroups to the XCDs round-robin)
-  a.t.xcd_remap = false;
+  a.tiling.xcd_remap = false;
   timed(phase, st, [&] {
-    launch_leapfrog_p2_boxes(sch_.lay, coef_, u_[old_], u_[cur_], u_[uf_[0]], u_[uf_[1]], boxes.data(),
-                             static_cast<int>(boxes.size()), d_s_ + 1, a.cts, a.mask, a.part, a.t, st, a.real,
-                             u.analytic, a.slots * n_tb_, n_tb_);
+    launch_leapfrog_p2_boxes(sch_.lay, coef_, boxes.data(), static_cast<int>(boxes.size()), a, st);
   });
   return true;
 }

@@ -43,6 +43,17 @@ bool throws(F&& f) {
   return false;
 }
 
+// f throws an error whose message contains `what`
+template <class F>
+bool throws_with(F&& f, const std::string& what) {
+  try {
+    f();
+  } catch (const std::exception& e) {
+    return std::string(e.what()).find(what) != std::string::npos;
+  }
+  return false;
+}
+
 // split_axis: the parts tile 0..N exactly once, interior work differs by at most one node between parts
 void test_split_axis() {
   for (i64 N : {2, 3, 7, 64, 127, 512, 2048}) {
@@ -568,10 +579,16 @@ int check_unit_grids(const RankSchedule& s, const UnitPlan& u, int target) {
   const int slot = tb_slot_blocks(s.lay, s.full, tmax, s.mode == Mode::kDeepTb);
   CHECK(slot > 0 && (!t.xcd_remap || slot % 8 == 0));
   t.stages = u.steps;
-  // one launch per box (GpuSolver::tb_pass): the pair-tiled kernel where it applies, else k_leapfrog_tb (S ≤ 4)
+  // one launch per box (GpuSolver::tb_pass): the pair-tiled kernel where it applies, else k_leapfrog_tb (S ≤ 4).
+  // (These schedules have no push transport, and no fused pack where tiling.p2 is set.) Either kernel's box checks
+  // accept the box with the schedule's stage-real ranges.
+  const LBox real = s.mode == Mode::kDeepTb ? s.sreal : tb_default_real();
+  auto kernel = [&](const LBox& b) { return pass_kernel(s.lay, b, u.steps, t.p2, u.analytic, false, false); };
   auto one = [&](const LBox& b) {
     if (b.empty()) return;
-    if (t.p2 && leapfrog_p2_supported(s.lay, b, u.steps) && !(u.analytic && u.steps > 4)) {
+    CHECK(!throws([&] { pass_box_check(s.lay, b, u.steps, real, "leapfrog_tb", true); }));
+    CHECK(!throws([&] { pass_box_check(s.lay, b, u.steps, real, "leapfrog_p2", false); }));
+    if (kernel(b) == PassKernel::kP2) {
       const P2LaunchGrid g = p2_launch_grid(&b, 1, t);
       check_box_grid(g.box[0], b, p2_max_xlen(u.steps));
       CHECK(g.box[0].blk0 == 0 && g.nactive == g.box[0].blocks() && g.nblocks >= g.nactive);
@@ -580,7 +597,7 @@ int check_unit_grids(const RankSchedule& s, const UnitPlan& u, int target) {
       CHECK(u.steps <= 4);
       const PassBoxGrid g = tb_box_grid(b, t);
       check_box_grid(g, b, 1 << 30);
-      CHECK(tb_round(g.blocks(), t) <= slot);
+      CHECK(pass_round(g.blocks(), t) <= slot);
     }
   };
   one(u.interior);
@@ -588,7 +605,7 @@ int check_unit_grids(const RankSchedule& s, const UnitPlan& u, int target) {
   if (u.shells.size() < 2) return 0;
   // all shells in one launch (GpuSolver::tb_pass_boxes): only where the combined grid fits the slot
   const int n = static_cast<int>(u.shells.size());
-  const int used = tb_shells_launch_blocks(s.lay, u.shells.data(), n, t, slot);
+  const int used = tb_shells_launch_blocks(s.lay, u.shells.data(), n, t, slot, u.analytic);
   CHECK(used <= slot);
   if (n > kP2MaxBoxes) {
     CHECK(used == 0);
@@ -599,10 +616,10 @@ int check_unit_grids(const RankSchedule& s, const UnitPlan& u, int target) {
   const P2LaunchGrid g = p2_launch_grid(u.shells.data(), n, tc);
   int blk = 0;
   i64 tiles = 0;
-  bool p2 = t.p2;
+  bool p2 = true;
   for (int k = 0; k < n; ++k) {
     const LBox& b = u.shells[static_cast<size_t>(k)];
-    p2 = p2 && leapfrog_p2_supported(s.lay, b, u.steps);
+    p2 = p2 && kernel(b) == PassKernel::kP2;
     check_box_grid(g.box[k], b, p2_max_xlen(u.steps));
     CHECK(g.box[k].blk0 == blk);  // prefix sums
     blk += g.box[k].blocks();
@@ -684,6 +701,133 @@ void test_pass_grids() {
   CHECK(over > 0);  // (the sweep reaches the regime the slot check exists for)
 }
 
+i64& edge(LBox& b, int axis, int side) {
+  i64* const e[3][2] = {{&b.x0, &b.x1}, {&b.y0, &b.y1}, {&b.z0, &b.z1}};
+  return *e[axis][side];
+}
+Layout block_layout(i64 N, const Dims& d, int rank, i64 g) {
+  Problem pr;
+  pr.N = N;
+  return make_layout(pr, rank_box(pr, d, rank), 16, g, g, g);
+}
+
+// The rule that says which kernel family takes a launch (pass_grid.hpp pass_kernel): every condition flips the answer
+// on its own.
+void test_pass_kernel() {
+  const PassKernel kP2 = PassKernel::kP2, kTb = PassKernel::kTb;
+  int odd_ends = 0;
+  for (const Layout& l : {block_layout(40, Dims{1, 1, 1}, 0, 1), block_layout(40, Dims{2, 2, 2}, 0, 3),
+                          block_layout(40, Dims{2, 2, 2}, 7, 3)}) {
+    const LBox full = compute_box(l);
+    CHECK(!full.empty() && full.z1 - full.z0 >= 8);
+    for (int S = 2; S <= 5; ++S) CHECK(pass_kernel(l, full, S, true, false, false, false) == kP2);
+    CHECK(pass_kernel(l, full, 4, false, false, false, false) == kTb);  // tiling.p2 off
+    CHECK(pass_kernel(l, full, 4, true, false, true, false) == kTb);    // push transport on
+    CHECK(pass_kernel(l, full, 4, true, false, false, true) == kTb);    // fused pack present
+    // 16-byte pairs: a box starts on a pair ...
+    LBox b = full;
+    b.z0 = full.z0 + 1;
+    CHECK(pass_kernel(l, b, 4, true, false, false, false) == kTb);
+    b.z0 = full.z0 + 2;
+    CHECK(pass_kernel(l, b, 4, true, false, false, false) == kP2);
+    // ... and ends on a whole one, unless it ends at the rank's last node
+    b = full;
+    b.z1 = full.z0 + 3;
+    CHECK(pass_kernel(l, b, 4, true, false, false, false) == kTb);
+    b.z1 = full.z0 + 4;
+    CHECK(pass_kernel(l, b, 4, true, false, false, false) == kP2);
+    b.z0 = full.z0 + 2 * ((full.z1 - full.z0 - 3) / 2);  // the last 3 (or 4) nodes: half a pair at the end, or none
+    b.z1 = full.z1;
+    odd_ends += (b.z1 - b.z0) % 2;
+    CHECK(pass_kernel(l, b, 4, true, false, false, false) == kP2);
+    for (int cut = 0; cut < 2; ++cut) {
+      --b.z1;
+      CHECK(pass_kernel(l, b, 4, true, false, false, false) == ((b.z1 - b.z0) % 2 == 0 ? kP2 : kTb));
+    }
+    // the analytic start takes at most 4 steps
+    CHECK(pass_kernel(l, full, 4, true, true, false, false) == kP2);
+    CHECK(pass_kernel(l, full, 5, true, true, false, false) == kTb);
+    CHECK(pass_kernel(l, full, 5, true, false, false, false) == kP2);
+    // S = 5 without the pair-tiled kernel: k_leapfrog_tb's launcher, which then refuses the depth
+    CHECK(pass_kernel(l, full, 5, false, false, false, false) == kTb);
+  }
+  CHECK(odd_ends >= 1);
+}
+
+// The box checks both launchers share (pass_grid.hpp pass_box_check), on ranks of a 3 × 3 × 3 world at N = 40 with
+// 3-deep ghosts: the middle rank, and the two corner ranks at the global boundary.
+void test_pass_box_check() {
+  const Dims d{3, 3, 3};
+  const Layout mid = block_layout(40, d, 13, 3), low = block_layout(40, d, 0, 3), high = block_layout(40, d, 26, 3);
+  LBox fmid = compute_box(mid), flow = compute_box(low), fhigh = compute_box(high);
+  // stage-real ranges as the schedule sets them: T1 nodes beyond every face with a neighbour
+  auto real_of = [&](const Layout& l, int rank, i64 T1) {
+    LBox r = compute_box(l);
+    for (int a = 0; a < 3; ++a) {
+      if (neighbor_rank(d, rank, a, 0) >= 0) edge(r, a, 0) -= T1;
+      if (neighbor_rank(d, rank, a, 1) >= 0) edge(r, a, 1) += T1;
+    }
+    return r;
+  };
+  // the compute box, one node in from both ends of every axis but `axis`
+  auto shrunk = [](const Layout& l, int axis) {
+    LBox b = compute_box(l);
+    for (int a = 0; a < 3; ++a)
+      if (a != axis) ++edge(b, a, 0), --edge(b, a, 1);
+    return b;
+  };
+  auto check = [](const Layout& l, const LBox& b, i64 S, const LBox& real, bool tb) {
+    return pass_box_check(l, b, S, real, tb ? "leapfrog_tb" : "leapfrog_p2", tb);
+  };
+  const char* ax[3] = {"x", "y", "z"};
+  // a defaulted real range: x the compute box, y / z the whole allocation
+  {
+    const LBox r = check(low, shrunk(low, -1), 2, tb_default_real(), true), f = compute_box(low);
+    CHECK(r.x0 == f.x0 && r.x1 == f.x1 && r.y0 == -3 && r.y1 == low.ny + 3 && r.z0 == -3 && r.z1 == low.nz + 3);
+    const LBox q = check(low, shrunk(low, -1), 2, LBox{1, 0, -2, 5, 1, 0}, false);
+    CHECK(q.x0 == f.x0 && q.x1 == f.x1 && q.y0 == -2 && q.y1 == 5);
+  }
+  for (bool tb : {true, false})
+    for (int a = 0; a < 3; ++a) {
+      const std::string name = tb ? "leapfrog_tb: " : "leapfrog_p2: ";
+      // S = 4 reads 4 nodes beyond the box: deeper than 3 ghosts on either end of the middle rank ...
+      for (int side = 0; side < 2; ++side) {
+        LBox b = shrunk(mid, -1);
+        edge(b, a, side) = edge(fmid, a, side);
+        CHECK(throws_with([&] { check(mid, b, 4, real_of(mid, 13, 3), tb); },
+                          name + "halo deeper than the ghosts in " + ax[a]));
+        CHECK(!throws([&] { check(mid, b, 3, real_of(mid, 13, 3), tb); }));
+        // ... but beyond the global boundary nothing is read: the same box of a corner rank, at its boundary end
+        const Layout& c = side == 0 ? low : high;
+        LBox bc = shrunk(c, -1);
+        edge(bc, a, side) = edge(side == 0 ? flow : fhigh, a, side);
+        CHECK(!throws([&] { check(c, bc, 4, real_of(c, side == 0 ? 0 : 26, 3), tb); }));
+      }
+      // a real range beyond the allocation, a stage-1 range that ends at the box: x in both kernels, y / z in
+      // k_leapfrog_tb (the pair-tiled pass has no y / z real range and ignores it)
+      LBox wide = real_of(mid, 13, 1), narrow = real_of(mid, 13, 2);
+      edge(wide, a, 0) = -4;
+      edge(narrow, a, 1) = edge(fmid, a, 1);
+      if (tb || a == 0) {
+        CHECK(throws_with([&] { check(mid, shrunk(mid, -1), 2, wide, tb); },
+                          name + "real range outside the allocation in " + ax[a]));
+        CHECK(throws_with([&] { check(mid, shrunk(mid, a), 3, narrow, tb); },
+                          name + "stage-1 range does not cover the box halo in " + ax[a]));
+      } else {
+        CHECK(!throws([&] { check(mid, shrunk(mid, -1), 2, wide, tb); }));
+        CHECK(!throws([&] { check(mid, shrunk(mid, a), 3, narrow, tb); }));
+      }
+      CHECK(!throws([&] { check(mid, shrunk(mid, a), 3, real_of(mid, 13, 2), tb); }));
+      // a box that leaves the compute box: k_leapfrog_tb only (the pair-tiled pass has its own box rule)
+      LBox out = shrunk(mid, -1);
+      edge(out, a, 0) = -1;
+      if (tb)
+        CHECK(throws_with([&] { check(mid, out, 2, real_of(mid, 13, 3), tb); }, "leapfrog_tb box outside the compute box"));
+      else
+        CHECK(!throws([&] { check(mid, out, 2, real_of(mid, 13, 3), tb); }));
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -699,6 +843,8 @@ int main() {
   test_deep_tb_worlds();
   test_traffic();
   test_pass_grids();
+  test_pass_kernel();
+  test_pass_box_check();
   std::printf("test_core: %d checks, %d failed\n", g_checks, g_fail);
   return g_fail == 0 ? 0 : 1;
 }

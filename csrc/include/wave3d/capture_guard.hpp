@@ -17,17 +17,23 @@
 
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <string>
 
 namespace wave3d::capture {
 
-void begin(hipStream_t origin);            // after hipStreamBeginCapture(origin)
+void begin(hipStream_t origin);            // once the capture on `origin` has begun
 void record(hipEvent_t e, hipStream_t s);  // hipEventRecord(e, s) + bookkeeping while a capture is active
 void wait(hipStream_t s, hipEvent_t e);    // hipStreamWaitEvent(s, e, 0); throws (fail) on the crashing topology
 void finish();                             // the schedule is enqueued: stop tracking
 void close();                              // an aborted capture: join every stream into its parent, stop tracking
 void abandon();                            // after hipStreamEndCapture: release close()'s events, forget the state
 bool active();
+
+// One captured schedule, ready to replay: begin capture on `origin`, begin(), enqueue() then finish() (enqueue threw:
+// close(), its message to *thrown), end capture, abandon(), instantiate, upload. Returns the executable graph, or
+// nullptr when any step failed (the last HIP error is cleared). W3D_DEBUG: the steps' results on stderr.
+hipGraphExec_t graph(hipStream_t origin, const std::function<void()>& enqueue, std::string* thrown);
 
 // the probe topologies through the guard, captured and launched on the current device (tests): mode 0 = one copy
 // stream per face (production), 2 = the round-4 split. Returns "ok" or the refusal message.

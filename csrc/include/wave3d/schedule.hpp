@@ -204,4 +204,15 @@ struct Traffic {
 };
 Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool init_kernel);
 
+// The global error log from the ranks' logs. Rank q's entry of step n is the pair xy[(q·(K+1) + n)·2 + {0, 1}] = (max
+// |e|, Σe²) over its nodes; per step of `checked`, in fixed rank order: the maximum (a NaN sticks) and Σe² summed left
+// to right.
+struct ErrorLog {
+  std::vector<int> steps;       // checked steps
+  std::vector<double> max_err;  // L∞ (global)
+  std::vector<double> rms_err;  // sqrt(Σe² / (N−1)³) (global)
+  bool finite = true;           // no maximum and no Σe² is NaN or infinite
+};
+ErrorLog combine_error_log(const double* xy, int nsrc, int K, int N, const std::vector<int>& checked);
+
 }  // namespace wave3d

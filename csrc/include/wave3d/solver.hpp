@@ -44,14 +44,10 @@ struct UnitTrace {
   double shell_ms = 0, comm_ms = 0, compute_ms = 0, check_ms = 0;
 };
 
-struct RunResult {
-  std::vector<int> steps;         // checked steps
-  std::vector<double> max_err;    // L∞ (global)
-  std::vector<double> rms_err;    // sqrt(Σe² / (N−1)³) (global)
+struct RunResult : ErrorLog {     // (schedule.hpp: steps, max_err, rms_err, finite)
   double solve_s = 0.0;           // host wall time of run(): field init → last error gathered
   PhaseTimes phases;              // only with SolverOptions::timers
   std::vector<UnitTrace> trace;   // per unit, only with SolverOptions::timers
-  bool finite = true;
   bool batched = false;           // run_batch's pipelined path: solve_s is the batch's wall time / n
 };
 
@@ -190,8 +186,10 @@ class GpuSolver {
   bool needs_exchange(int i) const { return units_[static_cast<size_t>(i)].exchange; }
   hipStream_t xstream() const { return sch_.side_stream() ? s1_ : s0_; }
   void phase_init();
+  void check_stored(int n, const double* buf);  // phase_init: the stored u^n (step 1's check) → the error log
   void unit_shell(int i);
   void unit_exchange_rccl(int i);
+  void unit_exchange(int i) { sch_.sdma ? unit_exchange_sdma(i) : unit_exchange_rccl(i); }  // by the transport in use
   void unit_interior(int i);
   // What the LDS pass launches of unit u share: the buffers, the tiling, time factors and check mask of its levels, its
   // slot of partials (counted in tb_slots_ when a level is checked) and the stage-real ranges.
@@ -244,6 +242,10 @@ class GpuSolver {
   static constexpr int kTbLevels = 5; // levels per pass (5-step passes: k_leapfrog_p2)
   Partial* tb_partials_ = nullptr;
   int tb_region_ = 0;
+  // a level's partials within a region: a unit's launch slots (kTbSlots on multi-rank ranks, else 1) of n_tb_ each
+  int tb_level_stride() const { return (sch_.mode == Mode::kDeepTb ? kTbSlots : 1) * n_tb_; }
+  Partial* tb_region(int r) const { return tb_partials_ + r * (kTbLevels * tb_level_stride()); }
+  size_t tb_bytes_ = 0, send_bytes_ = 0, recv_bytes_ = 0;  // allocated: tb_partials_, send_buf_, recv_buf_
   std::vector<ReduceJob> pending_;
   void flush_reduces();
   int cur_ = 1, old_ = 0;                     // buffer roles during enqueue
@@ -278,7 +280,7 @@ class GpuSolver {
   // --poison-ghosts: NaN into the ghost regions u's exchange fills (uf: the buffers u's pass writes); before_pass: into
   // the ghost plane u's passes store themselves (UnitPlan::ghost_bits), issued by unit_shell before their launches
   void poison(const UnitPlan& u, const int uf[2], hipStream_t st, bool before_pass = false);
-  // push transport (slab deep-tb)
+  // push transport (slab deep-tb; transport_push.cpp)
   double* stg_ = nullptr;       // [parity][field (0: u^{n+S−1}, 1: u^{n+S})][side (0: lo ghosts, 1: hi)][T planes]
   unsigned* flags_ = nullptr;   // uncached: [0] raised by the lower neighbour, [1] by the upper, [4] timeout, [8] done
   double* peer_stg_[2] = {nullptr, nullptr};   // neighbours' staging (lo, hi)
@@ -292,6 +294,10 @@ class GpuSolver {
   mutable unsigned push_uid_ = 0;              // solver instance number (table tags)
   i64 stg_off(int par, int field, int side) const { return ((par * 2 + field) * 2 + side) * sch_.lay.xg * sch_.lay.plane; }
   void connect_push_peer(int side, double* stg, unsigned* flags, bool ipc);
+  void push_alloc();                 // constructor: staging, flags, pass tables
+  void push_begin_solve();           // s0, start of a solve: reset the signal counter (--poison-ghosts: NaN staging)
+  void push_upload();                // s0, once units_ is planned: every pass's TbPush → push_dev_
+  void push_pass_args(PassArgs& a);  // the current unit's table entries (and its command-processor waits, on s0)
   void push_finish(hipStream_t st);  // end of a solve: zero this rank's flags (after its last wait)
   void push_check();                 // after a solve: fail if a wait timed out
   // copy-engine transport (transport_sdma.cpp). Link k = one neighbour (schedule.hpp LinkPlan). This rank's flag
@@ -396,6 +402,7 @@ class GpuGroup {
  private:
   void enqueue();
   void join();
+  void wire_sdma();  // copy-engine ranks: every link's peer pointers
   std::vector<std::unique_ptr<GpuSolver>> ranks_;
   std::string transport_;
   bool graph_ = false;

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
+#include <exception>
 #include <map>
 #include <vector>
 
@@ -86,6 +88,44 @@ void close() {
 }
 
 void finish() { st.on = false; }
+
+hipGraphExec_t graph(hipStream_t origin, const std::function<void()>& enqueue, std::string* thrown) {
+  const bool dbg = std::getenv("W3D_DEBUG") != nullptr;
+  hipGraph_t g = nullptr;
+  hipGraphExec_t x = nullptr;
+  bool ok = hipStreamBeginCapture(origin, hipStreamCaptureModeThreadLocal) == hipSuccess;
+  if (dbg) std::fprintf(stderr, "[capture] begin capture ok=%d\n", ok ? 1 : 0);
+  if (ok) {
+    begin(origin);  // (every cross-stream wait checked)
+    try {
+      enqueue();
+      finish();
+    } catch (const std::exception& ex) {
+      ok = false;
+      *thrown = ex.what();
+      if (dbg) std::fprintf(stderr, "[capture] enqueue failed: %s\n", ex.what());
+      close();
+    }
+    const hipError_t e = hipStreamEndCapture(origin, &g);
+    abandon();
+    if (dbg) std::fprintf(stderr, "[capture] end capture: %s graph=%p\n", hipGetErrorString(e), static_cast<void*>(g));
+    ok = ok && e == hipSuccess && g != nullptr;
+  }
+  if (ok) {
+    const hipError_t e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
+    if (dbg) std::fprintf(stderr, "[capture] instantiate: %s\n", hipGetErrorString(e));
+    ok = e == hipSuccess;
+    // (upload now rather than at the first replay; the copy-engine runs still show one 9-12 ms solve among their first
+    // 2-7 — never later — with or without it: profiles/r4/sdma_streams.md. bench.py warms copy-engine runs up longer)
+    if (ok && hipGraphUpload(x, origin) != hipSuccess) {
+      (void)hipGraphExecDestroy(x);  // (instantiated but not uploadable: release it)
+      ok = false;
+    }
+  }
+  if (g) (void)hipGraphDestroy(g);
+  (void)hipGetLastError();
+  return ok ? x : nullptr;
+}
 
 std::string selftest(int mode) {
   // (multi-stream captures need the ROCm 7.2 runtime: the HIP 7.0 one PyTorch bundles crashes on per-unit joins even

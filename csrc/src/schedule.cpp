@@ -2,6 +2,7 @@
 #include "wave3d/schedule.hpp"
 
 #include <algorithm>
+#include <cmath>
 
 #include "wave3d/pass_grid.hpp"
 
@@ -372,6 +373,26 @@ Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool 
                    static_cast<double>(units.empty() ? 0 : units.size() - 1);
   }
   return t;
+}
+
+ErrorLog combine_error_log(const double* xy, int nsrc, int K, int N, const std::vector<int>& checked) {
+  ErrorLog r;
+  const size_t per = static_cast<size_t>(K + 1);
+  const double n_int = static_cast<double>(N - 1);
+  const double denom = n_int * n_int * n_int;
+  for (int n : checked) {
+    double m = 0.0, sum = 0.0;
+    for (int q = 0; q < nsrc; ++q) {  // fixed rank order
+      const double* v = xy + (static_cast<size_t>(q) * per + static_cast<size_t>(n)) * 2;
+      m = v[0] > m || std::isnan(v[0]) ? v[0] : m;
+      sum += v[1];
+    }
+    r.steps.push_back(n);
+    r.max_err.push_back(m);
+    r.rms_err.push_back(std::sqrt(sum / denom));
+    if (!std::isfinite(m) || !std::isfinite(sum)) r.finite = false;
+  }
+  return r;
 }
 
 }  // namespace wave3d

@@ -1,5 +1,5 @@
 // Native unit tests of the host-side core (no GPU): decomposition, layout, halo plans, scheme, CPU solver, and the
-// solve schedule (schedule.hpp: modes, unit lists, messages, shell boxes, traffic).
+// solve schedule (schedule.hpp: modes, unit lists, messages, shell boxes, traffic, the error-log combine).
 //
 // SURVEY.md §4.2 "unit (C++/ctest)": exact-arithmetic checks of the pieces every backend shares. Built and run by
 // CMake/ctest (CMakeLists.txt) and, with host AddressSanitizer + UBSan, by tests/test_native_unit.py.
@@ -555,6 +555,67 @@ void test_traffic() {
   }
 }
 
+// combine_error_log: three ranks' logs of a K = 4 solve checked at steps 2 and 4 into the global one. Fixed rank order,
+// a NaN maximum sticks, the finite flag, unchecked steps left out.
+void test_combine_error_log() {
+  const int K = 4, N = 5, P = 3;  // (N − 1)³ = 64
+  const double nan = std::nan(""), big = 1e16;
+  const std::vector<int> checked = {2, 4};
+  std::vector<double> xy;
+  auto at = [&](int q, int n) { return &xy[static_cast<size_t>((q * (K + 1) + n) * 2)]; };
+  // every entry of the unchecked steps 0, 1, 3 holds what must never show: NaN maxima, infinite sums
+  auto reset = [&] {
+    xy.assign(static_cast<size_t>(P * (K + 1) * 2), 0.0);
+    for (int q = 0; q < P; ++q)
+      for (int n : {0, 1, 3}) at(q, n)[0] = nan, at(q, n)[1] = INFINITY;
+  };
+  auto set = [&](int n, const double (&mx)[3], const double (&sum)[3]) {
+    for (int q = 0; q < P; ++q) at(q, n)[0] = mx[q], at(q, n)[1] = sum[q];
+  };
+  // Σe² in rank order: three values whose sum depends on the order, in two arrangements that tell left-to-right from
+  // every other order; the maximum held by the last rank (step 2) and by the first (step 4)
+  {
+    reset();
+    set(2, {0.25, 0.5, 0.75}, {big, 1.0, -big});
+    set(4, {3.0, 1.0, 2.0}, {big, -big, 1.0});
+    const ErrorLog r = combine_error_log(xy.data(), P, K, N, checked);
+    CHECK(r.steps == checked && r.max_err.size() == 2 && r.rms_err.size() == 2);
+    CHECK(r.max_err[0] == 0.75 && r.max_err[1] == 3.0);
+    double s2 = 0.0, s4 = 0.0;
+    for (double v : {big, 1.0, -big}) s2 += v;
+    for (double v : {big, -big, 1.0}) s4 += v;
+    CHECK(s2 == 0.0 && (big + -big) + 1.0 == 1.0);   // (step 2: left to right loses the 1 that first + last keeps)
+    CHECK(s4 == 1.0 && big + (-big + 1.0) == 0.0);   // (step 4: left to right keeps the 1 that right to left loses)
+    CHECK(r.rms_err[0] == std::sqrt(s2 / 64.0) && r.rms_err[1] == std::sqrt(s4 / 64.0) && r.rms_err[1] == 0.125);
+    CHECK(r.finite);
+  }
+  // a NaN maximum in the middle rank sticks for that step (a larger finite maximum follows it) and clears `finite`;
+  // the other step stays finite
+  {
+    reset();
+    set(2, {0.25, nan, 0.75}, {1.0, 2.0, 3.0});
+    set(4, {0.5, 0.125, 0.25}, {16.0, 16.0, 32.0});
+    const ErrorLog r = combine_error_log(xy.data(), P, K, N, checked);
+    CHECK(std::isnan(r.max_err[0]) && !r.finite);
+    CHECK(r.rms_err[0] == std::sqrt(6.0 / 64.0));
+    CHECK(r.max_err[1] == 0.5 && r.rms_err[1] == 1.0);
+    // ... the same log without the NaN is finite; an infinite sum alone is not
+    at(1, 2)[0] = 0.5;
+    CHECK(combine_error_log(xy.data(), P, K, N, checked).finite);
+    at(2, 4)[1] = INFINITY;
+    CHECK(!combine_error_log(xy.data(), P, K, N, checked).finite);
+  }
+  // one source (a one-rank solve, or a rank's own log): the first rank's entries alone; no checked step, an empty log
+  {
+    reset();
+    set(2, {0.25, 9.0, 9.0}, {64.0, 9.0, 9.0});
+    const ErrorLog r = combine_error_log(xy.data(), 1, K, N, {2});
+    CHECK(r.steps == std::vector<int>{2} && r.max_err[0] == 0.25 && r.rms_err[0] == 1.0 && r.finite);
+    const ErrorLog e = combine_error_log(xy.data(), P, K, N, {});
+    CHECK(e.steps.empty() && e.max_err.empty() && e.rms_err.empty() && e.finite);
+  }
+}
+
 // Workgroup counts of every LDS pass launch (pass_grid.hpp) against the partial slot the solver sizes once: an
 // over-wide grid — a launch asked for more workgroups than its slot holds — aborts the solve inside the graph capture
 // ("bad grid_blocks"). `over` counts the units whose combined shell launch, with only the parent's guard (Σ tiles ≤
@@ -842,6 +903,7 @@ int main() {
   test_mode_table();
   test_deep_tb_worlds();
   test_traffic();
+  test_combine_error_log();
   test_pass_grids();
   test_pass_kernel();
   test_pass_box_check();

@@ -63,8 +63,11 @@ LIB_SOURCES = [
     ("src/kernels_leapfrog_p2_box_s3.hip", "hip"),
     ("src/kernels_leapfrog_p2_box_s4.hip", "hip"),
     ("src/kernels_leapfrog_p2_box_s5.hip", "hip"),
+    ("src/comm.cpp", "hip"),
     ("src/solver_gpu.cpp", "hip"),
+    ("src/gpu_group.cpp", "hip"),
     ("src/capture_guard.cpp", "hip"),
+    ("src/transport_push.cpp", "hip"),
     ("src/transport_sdma.cpp", "hip"),
     ("src/runtime_launch.cpp", "hip"),
     ("src/runtime_io.cpp", "hip"),
@@ -89,7 +92,7 @@ def _hash_inputs(src: Path, flags: list[str]) -> str:
     h = hashlib.sha256()
     h.update(" ".join(flags).encode())
     h.update(src.read_bytes())
-    for hdr in sorted([*(CSRC / "include").rglob("*.hpp"), *(CSRC / "app").glob("*.hpp")]):
+    for hdr in sorted([*(CSRC / "include").rglob("*.hpp"), *(CSRC / "app").glob("*.hpp"), *(CSRC / "src").glob("*.hpp")]):
         h.update(hdr.read_bytes())
     return h.hexdigest()[:16]
 

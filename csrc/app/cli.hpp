@@ -25,6 +25,7 @@ struct Args {
   bool overlap = true;
   bool fused_pack = true;
   bool ghost_store = true;  // --no-ghost-store: slab passes do not store the u^{n+S-1} ghost plane (A/B)
+  bool keep_prev = false;   // --keep-prev: the last pass stores u^{K-1} too (A/B)
   bool graph = true;
   bool timers = false;
   bool debug_sync = false;

@@ -193,7 +193,8 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
     std::ofstream j(a.json);
     j << "{\"backend\": \"hip\", \"group\": " << a.group << box_json(a.prob) << ", \"transport\": " << jstr(a.group_transport)
       << ", \"graph\": " << (g.graph_enabled() ? "true" : "false") << ", \"schedule\": " << jstr(g.rank(0).mode())
-      << ", \"temporal\": " << g.rank(0).options().temporal << ", \"rccl_comms\": " << cc.size() << ", \"solve_s\": " << jnum(best) << ", \"steps\": [";
+      << ", \"temporal\": " << g.rank(0).options().temporal << ", \"stored_prev\": "
+      << (g.rank(0).stored_prev() ? "true" : "false") << ", \"rccl_comms\": " << cc.size() << ", \"solve_s\": " << jnum(best) << ", \"steps\": [";
     for (size_t i = 0; i < r.steps.size(); ++i)
       j << (i ? ", " : "") << "[" << r.steps[i] << ", " << jnum(r.max_err[i]) << ", " << jnum(r.rms_err[i]) << "]";
     j << "]}\n";
@@ -424,6 +425,7 @@ int run_gpu(const Args& a) {
         << (s->overlapped() ? "true" : "false") << ", \"overlap_requested\": " << (s->options().overlap ? "true" : "false")
         << ", \"temporal\": " << s->options().temporal
         << ", \"schedule\": " << jstr(sched) << ", \"mode\": " << jstr(s->mode())
+        << ", \"stored_prev\": " << (s->stored_prev() ? "true" : "false")
         << ", \"transport\": " << jstr(s->transport()) << ", \"device\": "
         << jstr(prop.gcnArchName) << ", \"bench_steps\": " << a.bench_steps << ", \"bench_s\": " << jnum(bench_s)
         << ", \"bench_pipelined\": " << (a.bench_steps > 0 && r.batched ? "true" : "false")

@@ -138,6 +138,8 @@ int leapfrog_tb_partials(const Layout& l, const LBox& box, const LeapfrogTbTilin
 struct PassArgs {
   const double *prev = nullptr, *cur = nullptr;  // u^{n−1}, u^n
   double *out1 = nullptr, *out2 = nullptr;       // u^{n+S−1}, u^{n+S}: four distinct buffers
+  // (out1 = nullptr, the pair-tiled pass only: u^{n+S−1} is not stored — a solve's last pass, whose u^{K−1} GpuSolver
+  // rebuilds on first use; out2 and the partials are what they are with out1 set. Not with tiling.ghost_x1.)
   const double* d_s = nullptr;                   // sin table, global index −1..N+1
   double ct[5] = {0, 0, 0, 0, 0};                // ct[k−1]: the time factor of u^{n+k}
   int check_mask = 0;            // bit k−1: error check of u^{n+k} ...
@@ -176,7 +178,7 @@ bool fill_pass_params(Params& p, const Layout& l, const Coeffs& c, const PassArg
   const i64 kb = (l.xg - 1) * l.plane;  // x base only: in-plane offsets are plane-relative (non-negative)
   p.prev = a.analytic_start ? nullptr : a.prev + kb;
   p.cur = a.analytic_start ? nullptr : a.cur + kb;
-  p.out1 = a.out1 + kb;
+  p.out1 = a.out1 != nullptr ? a.out1 + kb : nullptr;
   p.out2 = a.out2 + kb;
   p.s = a.d_s;
   p.tau2 = c.lam;  // τ²/h² and τ²/(2h²): the coefficients of d2sum

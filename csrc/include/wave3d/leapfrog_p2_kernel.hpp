@@ -250,7 +250,7 @@ constexpr int kP2Boxes = kP2MaxBoxes;
 struct P2Params {
   const double* prev;  // u^{n−1} (x base: local plane x at (x + 1)·plane, as TbParams)
   const double* cur;   // u^n
-  double* out1;        // u^{n+S−1}
+  double* out1;        // u^{n+S−1} (nullptr: not stored; the launcher then refuses ghost_x1 planes)
   double* out2;        // u^{n+S}
   const double* s;     // sin table, global index −1..N+1
   Partial* partials;   // stage k's block of partials at (k−1)·lstride
@@ -584,6 +584,10 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
     (void)phq;
 
     const int i0 = wx0 - S + 1, i1 = wx1 + S - 2 + (kSplitSt && o1x1 > wx1 ? 1 : 0);
+    // out1 == nullptr: level S−1 is not stored (the last pass of a solve, whose u^{K−1} nothing may ever read). A
+    // kernel argument, so the test is a scalar branch around the store (and the split stores' LDS read-back): the
+    // skipped store issues no vector-memory instruction
+    const bool st1 = p.out1 != nullptr;
     auto xreal = [&](int x) __attribute__((always_inline)) {
       return x >= p.sx0 && x < p.sx1 && inside(p.gx0 + x);
     };
@@ -681,7 +685,7 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
       if constexpr (kSplitSt && k == S) {
         if (winner) {
           store_pair(v, p.out2, xp, soff, xown);
-        } else {
+        } else if (st1) {
           constexpr int pl = (S - 2) * 2 + (D & 1);  // level S−1, plane xp: written by stage S−1 last iteration
           store_pair(rd2(rt, ok_(pl, 0, 0)), p.out1, xp, soff2, xown1);
         }
@@ -690,7 +694,8 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
         // Passes that load: every wave stores (non-owners beyond the plane: dropped), so every wave's vector-memory
         // sequence is the same and the compiler's waits for the loads can leave the stores in flight. The analytic
         // start loads nothing: only the own waves store (−2 %)
-        if (!INIT || winner) store_pair(v, k == S ? p.out2 : p.out1, xp, soff, (k == S ? xown : xown1) && winner);
+        if ((!INIT || winner) && (k == S || st1))
+          store_pair(v, k == S ? p.out2 : p.out1, xp, soff, (k == S ? xown : xown1) && winner);
       }
     };
 

@@ -60,6 +60,10 @@ struct SolverOptions {
   // u^{n+S−1} plane next to each neighbour face (it computes it anyway), so the exchange sends S planes of u^{n+S} and
   // S − 2 (not S − 1) of u^{n+S−1} per face — 8 instead of 9 planes for a 5-step pass (A/B: --no-ghost-store)
   bool ghost_store = true;
+  // false: a solve's last pair-tiled pass stores u^K only (UnitPlan::drop_prev) and u^{K−1} is rebuilt when something
+  // first asks for it (GpuSolver: energy(0), download(1), field_hash(1)); true: every pass stores both levels (A/B:
+  // --keep-prev)
+  bool keep_prev = false;
   // deep-tb with overlap: the shell boxes run on the side stream concurrently with the interior (true), or on s0 before
   // it (false: they get the whole GPU and finish first, so the exchange starts earlier — measured faster with the copy
   // engines at 512³ and 2048³; concurrent helps the small block shells when no transfer follows; env W3D_SHELLS)
@@ -155,6 +159,11 @@ struct UnitPlan {
   // regions would become L-shaped messages), and only where every pass of the unit runs on the pair-tiled kernel.
   // Every rank computes the same bits for the same exchange, so both ends of a face agree on the message size.
   int ghost_bits = 0;
+  // the pass does not store u^{n+steps−1}: the LAST unit of a solve when it is a fused pass on the pair-tiled kernel
+  // with no exchange, four field buffers are in use, the transport is not push (nor the copy engines under
+  // poison_ghosts, whose end of solve writes into the unit's inputs) and SolverOptions::keep_prev is off.
+  // Decided from integers every rank shares, so the ranks of a world agree.
+  bool drop_prev = false;
   std::vector<MsgPlan> msgs;
   // deep-tb with overlap: the boxes the neighbours receive, computed first (cpu.hpp deep_split with w = depth), and the
   // rest; otherwise no shells and the whole compute box
@@ -198,7 +207,8 @@ std::vector<LinkPlan> plan_links(const RankSchedule& s);
 // device-memory traffic over the nodes this rank updates — a fused pass reads u^n, u^{n−1} and writes two levels,
 // an analytic-start pass only writes its two, a single step reads two and writes one, the init kernel writes two;
 // tile-halo re-reads that miss L2 are not in it (rocprof FETCH_SIZE counts those). halo_bytes: what this rank sends
-// its neighbours per solve (RCCL / copy-engine messages, or the push transport's forwarded face planes).
+// its neighbours per solve (RCCL / copy-engine messages, or the push transport's forwarded face planes). A level the
+// last pass leaves out (UnitPlan::drop_prev) is still counted: the figure describes the schedule, not that saving.
 struct Traffic {
   double field_bytes = 0.0, halo_bytes = 0.0;
 };

@@ -161,6 +161,9 @@ class GpuSolver {
   // Bytes the last run() moved (schedule.hpp traffic; units_ is rebuilt at the start of every solve)
   using Traffic = wave3d::Traffic;
   Traffic traffic() const { return wave3d::traffic(sch_, units_, !analytic_ && resume_n_ == 0); }
+  // whether the last solve's passes stored u^{K−1} themselves (false: its last pass left it out, UnitPlan::drop_prev,
+  // and the first of energy(0), download(1), field_hash(1) rebuilds it)
+  bool stored_prev() const { return units_.empty() || !units_.back().drop_prev; }
 
  private:
   friend class GpuGroup;
@@ -194,6 +197,16 @@ class GpuSolver {
   // What the LDS pass launches of unit u share: the buffers, the tiling, time factors and check mask of its levels, its
   // slot of partials (counted in tb_slots_ when a level is checked) and the stage-real ranges.
   PassArgs tb_args(const UnitPlan& u);
+  // ... the part that needs no slot: buffers (indices into u_), tiling, time factors, stage-real ranges; no check
+  PassArgs tb_args_fields(const UnitPlan& u, int prev, int cur, int out1, int out2) const;
+  // The last pass of a solve may leave u^{K−1} out (UnitPlan::drop_prev). After every solve (run, each solve of
+  // run_batch, a GpuGroup's run; so also the first one after set_state / set_initial) solve_done() notes whether it
+  // did; energy(0), download(1) and field_hash(1) then call materialise_prev(), which relaunches that one unit with
+  // both outputs (bit-identical: see its definition) and clears the mark.
+  void solve_done() { prev_missing_ = !units_.empty() && units_.back().drop_prev; }
+  void materialise_prev() const;
+  mutable bool prev_missing_ = false;  // u_[prev_buf_] does not hold the last solve's u^{K−1} yet
+  int last_in_[2] = {0, 1};            // buffers the last unit read: u^{n−1}, u^n
   // whether unit u's passes pack the z faces of the exchange that follows it (entry u.depth of pk_host_ / pk_dev_)
   bool tb_packs(const UnitPlan& u) const { return pk_dev_ != nullptr && u.exchange && pk_host_[u.depth].w == u.depth; }
   void tb_pass(const UnitPlan& u, const LBox& box, int phase, hipStream_t st = nullptr);  // one k_leapfrog_tb launch

@@ -663,6 +663,7 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("fake_traffic", &SolverOptions::fake_traffic)
       .def_readwrite("fused_pack", &SolverOptions::fused_pack)
       .def_readwrite("ghost_store", &SolverOptions::ghost_store)
+      .def_readwrite("keep_prev", &SolverOptions::keep_prev)
       .def_readwrite("sdma_streams", &SolverOptions::sdma_streams)
       .def_readwrite("flag_timeout_s", &SolverOptions::flag_timeout_s)
       .def_readwrite("push_no_collective", &SolverOptions::push_no_collective)
@@ -773,11 +774,16 @@ PYBIND11_MODULE(_C, m) {
       }, py::arg("phi"), py::arg("psi") = py::none())
       .def("energy", &GpuSolver::energy, py::arg("which") = 0,
            "discrete energy E^{K-1/2} (which = 0) / E^{1/2} (which = 1, after set_initial); one rank only")
+      .def("energy_sums", [](const GpuSolver& s, int which) {
+             const Partial e = s.energy_sums(which);
+             return py::make_tuple(e.x, e.y);
+           }, py::arg("which") = 0, "the kinetic and potential sums energy() is formed from")
       .def("shell_boxes", &GpuSolver::shell_boxes)
       .def("interior_box", &GpuSolver::interior_box)
       .def("check_steps", &GpuSolver::check_steps)
       .def("device_bytes", &GpuSolver::device_bytes)
       .def_property_readonly("mode", &GpuSolver::mode)
+      .def_property_readonly("stored_prev", &GpuSolver::stored_prev)
       .def_property_readonly("graph_enabled", [](const GpuSolver& s) { return s.options().graph; });
 
   // the CLI's multi-rank schedule autotune (runtime_autotune.cpp): same candidates, same rules; collectives over the
@@ -837,6 +843,7 @@ PYBIND11_MODULE(_C, m) {
       .def("layout", [](GpuGroup& g, int rank) { return g.rank(rank).layout(); })
       .def("dims", [](GpuGroup& g) { return g.rank(0).dims(); })
       .def("mode", [](GpuGroup& g) { return g.rank(0).mode(); })
+      .def("stored_prev", [](GpuGroup& g, int rank) { return g.rank(rank).stored_prev(); }, py::arg("rank") = 0)
       .def("temporal", [](GpuGroup& g) { return g.rank(0).options().temporal; },
            "pass depth every rank runs (the constructor lowers the requested depth where a schedule needs it)")
       .def("overlapped", [](GpuGroup& g) { return g.rank(0).overlapped(); })

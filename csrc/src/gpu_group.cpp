@@ -310,6 +310,7 @@ RunResult GpuGroup::run() {
   for (auto* s : rs) {
     if (s->comm_) s->comm_->check_async();
     s->push_check();
+    s->solve_done();
   }
   RunResult r;
   rs[0]->decode_log(all.data(), static_cast<int>(rs.size()), r);  // (every rank has the same schedule and check steps)

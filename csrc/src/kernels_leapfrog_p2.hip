@@ -197,10 +197,14 @@ void leapfrog_p2_prepare() {
 void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const LBox* boxes, int nbox, const PassArgs& a,
                               hipStream_t stream) {
   const LeapfrogTbTiling& t = a.tiling;
+  // out1 = null: u^{n+S−1} is not stored at all, so nothing may depend on its ghost planes (an exchange after the
+  // pass, or z-face packing, never reaches this launcher without one of them: pass_kernel)
+  W3D_REQUIRE(a.out1 != nullptr || (t.ghost_x1 == 0 && a.pack == nullptr && a.push == nullptr),
+              "leapfrog_p2: a pass without u^{n+S-1} (out1 = null) cannot store its ghost planes (ghost_x1) or pack");
   P2Params p = make_plan_p2(l, boxes, nbox, t, a.real, a.analytic_start);
   if (!fill_pass_params(p, l, c, a, "leapfrog_p2")) return;
   if (a.analytic_start) {  // (the analytic start reads neither: any valid buffer)
-    p.prev = p.out1;
+    p.prev = p.out2;
     p.cur = p.out2;
   }
 #ifdef W3D_EXPERIMENT_WGTIME

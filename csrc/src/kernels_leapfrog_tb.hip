@@ -90,6 +90,7 @@ void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const LBox& box, const
   }
   W3D_REQUIRE(t.stages <= 4, "leapfrog_tb: 5-step passes need the pair-tiled kernel (tiling.p2)");
   W3D_REQUIRE(t.ghost_x1 == 0, "leapfrog_tb: ghost-plane stores (tiling.ghost_x1) need the pair-tiled kernel");
+  W3D_REQUIRE(a.out1 != nullptr, "leapfrog_tb: a pass without u^{n+S-1} (out1 = null) needs the pair-tiled kernel");
   TbParams p = make_plan_tb(l, box, t, a.real);
   if (!fill_pass_params(p, l, c, a, "leapfrog_tb")) return;
   if (a.grid_blocks > 0) p.bby = p.bbz = 0;  // (a padded grid's extra workgroups have no tile)

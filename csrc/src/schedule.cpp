@@ -294,6 +294,14 @@ std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analyt
       W3D_REQUIRE(static_cast<int>(u.shells.size()) < kTbSlots, "deep-tb: too many shell boxes");
     }
   }
+  // nothing inside the solve reads the last pass's u^{K−1}: no pass follows, and no exchange sends it. (Not under
+  // --poison-ghosts on the copy-engine transport: its end of solve NaN-fills the ghost regions of buffers 2 and 3 for
+  // the next solve's first exchange, and those can be the last unit's inputs, which a rebuild reads again.)
+  if (nu > 0 && !s.opt.keep_prev && s.nbuf == 4 && !s.push && !(s.sdma && s.opt.poison_ghosts) &&
+      ((s.mode == Mode::kFusedSingle && s.opt.tb) || tb)) {
+    UnitPlan& u = units.back();
+    u.drop_prev = u.fused() && !u.exchange && runs_p2(s, u.steps, u.analytic);
+  }
   return units;
 }
 

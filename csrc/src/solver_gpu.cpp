@@ -254,6 +254,7 @@ Partial GpuSolver::energy_sums(int which) const {
   energy_alloc();
   const int n = energy_partials(sch_.lay);
   if (which == 0) {
+    materialise_prev();
     launch_energy(sch_.lay, coef_, sch_.prob.tau, u_[prev_buf_], u_[final_buf_], energy_part_, nullptr);
     launch_energy_reduce(energy_part_, n, energy_part_ + n, nullptr);
   }
@@ -497,28 +498,48 @@ void GpuSolver::unit_exchange_rccl(int i) {
   if (xs != s0_) capture::record(ev_halo_, xs);
 }
 
-PassArgs GpuSolver::tb_args(const UnitPlan& u) {
+PassArgs GpuSolver::tb_args_fields(const UnitPlan& u, int prev, int cur, int out1, int out2) const {
   PassArgs a;
-  a.prev = u_[old_];
-  a.cur = u_[cur_];
-  a.out1 = u_[uf_[0]];
-  a.out2 = u_[uf_[1]];
+  a.prev = u_[prev];
+  a.cur = u_[cur];
+  a.out1 = u_[out1];
+  a.out2 = u_[out2];
   a.d_s = d_s_ + 1;
   a.tiling = sch_.opt.tiling_tb;
   a.tiling.stages = u.steps;
   a.tiling.ghost_x1 = u.ghost_bits;
-  for (int k = 1; k <= u.steps; ++k) {
-    a.ct[k - 1] = ct_[static_cast<size_t>(u.n + k)];
-    if (is_check_[static_cast<size_t>(u.n + k)]) a.check_mask |= 1 << (k - 1);
-  }
-  a.level_stride = tb_level_stride();
-  W3D_REQUIRE((tb_slots_ + 1) * n_tb_ <= a.level_stride, "leapfrog_tb: too many launches in one unit");
-  // (every launch fills its whole slot of n_tb_ partials: shell and interior boxes may have fewer x chunks)
-  if (a.check_mask) a.partials = tb_region(tb_region_) + tb_slots_++ * n_tb_;
+  for (int k = 1; k <= u.steps; ++k) a.ct[k - 1] = ct_[static_cast<size_t>(u.n + k)];
   a.grid_blocks = n_tb_;
   a.real = sch_.mode == Mode::kDeepTb ? sch_.sreal : tb_default_real();
   a.analytic_start = u.analytic;
   return a;
+}
+
+PassArgs GpuSolver::tb_args(const UnitPlan& u) {
+  PassArgs a = tb_args_fields(u, old_, cur_, uf_[0], uf_[1]);
+  if (u.drop_prev) a.out1 = nullptr;  // (u^{n+S−1} of the solve's last pass: materialise_prev)
+  for (int k = 1; k <= u.steps; ++k)
+    if (is_check_[static_cast<size_t>(u.n + k)]) a.check_mask |= 1 << (k - 1);
+  a.level_stride = tb_level_stride();
+  W3D_REQUIRE((tb_slots_ + 1) * n_tb_ <= a.level_stride, "leapfrog_tb: too many launches in one unit");
+  // (every launch fills its whole slot of n_tb_ partials: shell and interior boxes may have fewer x chunks)
+  if (a.check_mask) a.partials = tb_region(tb_region_) + tb_slots_++ * n_tb_;
+  return a;
+}
+
+// u^{K−1} of a solve whose last pass left it out (UnitPlan::drop_prev): that one unit again, eagerly on s0 and outside
+// any graph, with out1 set. Its inputs are the two other buffers of the four-buffer rotation, ghost layers included, and
+// nothing has written them since the unit (it is the last, and it has no exchange), so the same kernel on the same
+// inputs stores the same bits — u^K over itself, and the missing level. No check and no partials: the error log, the
+// partial regions, pending reductions and the captured graph are not touched.
+void GpuSolver::materialise_prev() const {
+  if (!prev_missing_) return;
+  const UnitPlan& u = units_.back();
+  DeviceScope scope(dev_, true);
+  PassArgs a = tb_args_fields(u, last_in_[0], last_in_[1], prev_buf_, final_buf_);
+  launch_leapfrog_tb(sch_.lay, coef_, u.interior, a, s0_);
+  W3D_HIP(hipStreamSynchronize(s0_));
+  prev_missing_ = false;
 }
 
 // One LDS S-step pass of unit u over `box` on stream st (s0 unless given). Its checked levels' partials go to slot
@@ -619,6 +640,8 @@ void GpuSolver::unit_interior(int i) {
   if (wait && !joined) capture::wait(s0_, ev_halo_);
   if (chk && np > 0) timed(kPhaseCheck, s0_, [&] { launch_reduce(partials_, np, errlog_ + nc, s0_); });
   if (sch_.opt.debug_sync) W3D_HIP(hipDeviceSynchronize());
+  last_in_[0] = old_;
+  last_in_[1] = cur_;
   if (u.fused()) {
     old_ = uf_[0];
     cur_ = uf_[1];
@@ -801,6 +824,7 @@ RunResult GpuSolver::run() {
   collect_phases(r);
   ++runs_;
   if (initial_) ++initial_runs_;
+  solve_done();
   return r;
 }
 
@@ -844,6 +868,7 @@ std::vector<RunResult> GpuSolver::run_batch(int n) {
   xsolves_ += static_cast<unsigned>(n);
   runs_ += n;
   if (initial_) initial_runs_ += n;
+  solve_done();
   for (int i = 0; i < n; ++i) {
     RunResult r;
     decode_log(hbatch_ + static_cast<size_t>(i) * slot, nsrc, r);
@@ -858,6 +883,7 @@ std::vector<double> GpuSolver::download(int which) const {
   std::vector<double> h(static_cast<size_t>(sch_.lay.total));
   const double* src = u_[which == 0 ? final_buf_ : prev_buf_];
   DeviceScope scope(dev_, true);
+  if (which != 0) materialise_prev();
   W3D_HIP(hipMemcpy(h.data(), src, h.size() * sizeof(double), hipMemcpyDeviceToHost));
   return h;
 }
@@ -867,6 +893,7 @@ unsigned long long GpuSolver::field_hash(int which) const {
   unsigned long long* d = nullptr;
   W3D_HIP(hipMalloc(&d, sizeof(unsigned long long)));
   W3D_HIP(hipMemset(d, 0, sizeof(unsigned long long)));
+  if (which != 0) materialise_prev();
   launch_field_hash(sch_.lay, u_[which == 0 ? final_buf_ : prev_buf_], d, nullptr);
   unsigned long long h = 0;
   W3D_HIP(hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost));

@@ -99,7 +99,7 @@ class Solver:
                  debug_sync: bool = False, poison_ghosts: bool = False, deep_min_planes: int | None = None,
                  tb_min_planes: int | None = None, rccl: bool = True, autotune: bool = False,
                  autotune_rounds: int = 5, copy_engines: bool = False, fused_pack: bool = True,
-                 ghost_store: bool = True,
+                 ghost_store: bool = True, keep_prev: bool = False,
                  runtime: str = "inproc"):
         import torch.distributed as dist
 
@@ -136,7 +136,7 @@ class Solver:
                 raise ValueError("runtime='process': copy engines are the 'sdma' transport (transport='sdma')")
             for on, flag in ((timers, "--timers"), (debug_sync, "--debug-sync"), (poison_ghosts, "--poison-ghosts"),
                              (not tb, "--no-tb"), (not init2, "--no-init2"), (not fused_pack, "--no-fused-pack"),
-                             (not ghost_store, "--no-ghost-store")):
+                             (not ghost_store, "--no-ghost-store"), (keep_prev, "--keep-prev")):
                 if on:
                     flags.append(flag)
             for val, flag in ((tb_min_planes, "--tb-min-planes"), (deep_min_planes, "--deep-min-planes")):
@@ -159,7 +159,7 @@ class Solver:
         if self.backend == "hip" and self.transport in ("loopback", "rccl-self", "push", "sdma", "multi-device"):
             opts = self._options(C, decomp, spec, overlap, graph, tiling, temporal, tiling2, init2, tb, tiling_tb)
             opts.timers, opts.debug_sync, opts.poison_ghosts = timers, debug_sync, poison_ghosts
-            opts.fused_pack, opts.ghost_store = fused_pack, ghost_store
+            opts.fused_pack, opts.ghost_store, opts.keep_prev = fused_pack, ghost_store, keep_prev
             if deep_min_planes is not None:
                 opts.deep_min_planes = deep_min_planes
             if tb_min_planes is not None:
@@ -172,7 +172,7 @@ class Solver:
 
             opts = self._options(C, decomp, spec, overlap, graph, tiling, temporal, tiling2, init2, tb, tiling_tb)
             opts.timers, opts.debug_sync, opts.poison_ghosts = timers, debug_sync, poison_ghosts
-            opts.fused_pack, opts.ghost_store = fused_pack, ghost_store
+            opts.fused_pack, opts.ghost_store, opts.keep_prev = fused_pack, ghost_store, keep_prev
             if deep_min_planes is not None:
                 opts.deep_min_planes = deep_min_planes
             if tb_min_planes is not None:

@@ -109,6 +109,9 @@ constexpr Personality kPersonalities[] = {
                "                     from P.psi (wave3d-dump-v1, global fields; face values ignored). The error lines then\n"
                "                     are the difference from the eigenmode: use --energy\n"
                "  --energy           print the discrete energy E(1/2), E(K-1/2) and its drift (with --initial; one rank)\n"
+               "  --receivers FILE   record u at grid nodes for every step 0..K: FILE lists one node per line as i j k\n"
+               "                     (indices 0..N); the solve keeps its schedule (one GPU rank, --group, or --cpu)\n"
+               "  --traces OUT       write the recorded (K+1) x R values as OUT.bin (fp64, C order) + OUT.json\n"
                "  --force            run even if the CFL condition is violated\n"
                "  --quiet            only the summary\n");
   std::exit(2);
@@ -197,6 +200,8 @@ Args parse(int argc, char** argv) {
     else if (s == "--checkpoint") a.checkpoint = next();
     else if (s == "--resume") a.resume = next();
     else if (s == "--initial") a.initial = next();
+    else if (s == "--receivers") a.receivers = next();
+    else if (s == "--traces") a.traces = next();
     else if (s == "--energy") a.energy = true;
     else if (s == "--box") {
       const std::string v = next();  // LX,LY,LZ
@@ -249,6 +254,10 @@ Args parse(int argc, char** argv) {
   }
   if (!a.initial.empty() && !a.resume.empty()) usage("--initial and --resume exclude each other");
   if (a.energy && a.initial.empty()) usage("--energy needs --initial (E(1/2) is kept by solves that start from it)");
+  if (a.receivers.empty() != a.traces.empty()) usage("--receivers FILE and --traces OUT go together");
+  if (!a.receivers.empty() && a.np > 1)
+    usage("--receivers / --traces: one rank only (gathering traces from several processes is not implemented)");
+  if (!a.receivers.empty() && (a.serve || a.fake_rank >= 0)) usage("--receivers: not with --serve or --fake-rank");
   if (a.repeat < 1) a.repeat = 1;
   return a;
 }

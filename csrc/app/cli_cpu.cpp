@@ -23,6 +23,11 @@ int run_cpu(const Args& a) {
     load_initial(a.initial, a.prob, phi, psi);
     s.set_initial(phi.data(), psi.empty() ? nullptr : psi.data());
   }
+  std::vector<i64> nodes;
+  if (!a.receivers.empty()) {
+    nodes = load_receivers(a.receivers);
+    s.set_receivers(nodes.data(), static_cast<int>(nodes.size() / 3));
+  }
   if (a.serve) {  // (the rank-process protocol on the CPU solver: run / dump / quit — cli.hpp serve_loop)
     const std::string greeting = "{\"ready\": true, \"backend\": \"cpu\", \"rank\": 0, \"world\": 1, \"dims\": [1, 1, 1], "
                                  "\"schedule\": \"cpu-openmp\", \"mode\": \"cpu\", \"transport\": \"none\"}";
@@ -82,6 +87,7 @@ int run_cpu(const Args& a) {
       << ", \"steps\": " << steps_json(r.steps, r.max_err, r.rms_err) << "}\n";
   }
   if (!a.dump.empty()) write_dump(a.dump, a.prob, s.layout(), s.field(0), 0, 1, Dims{1, 1, 1});
+  if (!a.traces.empty()) write_traces(a.traces, a.prob, nodes, s.traces());
   if (!a.checkpoint.empty())
     write_checkpoint(a.checkpoint, a.prob, s.layout(), s.field(0), s.field(1), 0, 1, Dims{1, 1, 1});
   return r.finite ? 0 : 3;

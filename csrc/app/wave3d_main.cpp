@@ -122,6 +122,11 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
     load_initial(a.initial, a.prob, phi, psi);
     g.set_initial(phi.data(), psi.empty() ? nullptr : psi.data());
   }
+  std::vector<i64> nodes;
+  if (!a.receivers.empty()) {
+    nodes = load_receivers(a.receivers);
+    g.set_receivers(nodes.data(), static_cast<int>(nodes.size() / 3));
+  }
   if (a.serve) {
     // --group P --serve: all P ranks in this process (the Python Solver(world=P, runtime="process") of ONE Python
     // process); run / hash (summed over the ranks) / traffic (summed) / dump (one file per rank) / quit
@@ -184,6 +189,7 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
   if (!a.dump.empty())
     for (int q = 0; q < g.world(); ++q)
       write_dump(a.dump, a.prob, g.rank(q).layout(), g.rank(q).download(0), q, g.world(), d);
+  if (!a.traces.empty()) write_traces(a.traces, a.prob, nodes, g.traces());
   if (!a.checkpoint.empty())
     for (int q = 0; q < g.world(); ++q)
       write_checkpoint(a.checkpoint, a.prob, g.rank(q).layout(), g.rank(q).download(0), g.rank(q).download(1), q,
@@ -283,6 +289,13 @@ int run_gpu(const Args& a) {
     load_initial(a.initial, a.prob, phi, psi);
     s->set_initial(phi.data(), psi.empty() ? nullptr : psi.data());
   }
+  std::vector<i64> nodes;
+  if (!a.receivers.empty()) {
+    W3D_REQUIRE(world == 1, "--receivers / --traces: one rank only (gathering traces from several processes is not "
+                            "implemented)");
+    nodes = load_receivers(a.receivers);
+    s->set_receivers(nodes.data(), static_cast<int>(nodes.size() / 3));
+  }
   if (a.serve) {
     const int rc = serve(a, *s, hc, file_coll, sched);
     if ((s->push() || s->sdma()) && !comm && !fake)
@@ -354,6 +367,7 @@ int run_gpu(const Args& a) {
   const double e_start = a.energy ? s->energy(1) : 0.0, e_end = a.energy ? s->energy(0) : 0.0;
   // --dump: u^K of the last solve above (before the traced solve below overwrites the fields with its own)
   if (!a.dump.empty()) write_dump(a.dump, a.prob, s->layout(), s->download(0), rank, world, s->dims());
+  if (!a.traces.empty()) write_traces(a.traces, a.prob, nodes, s->traces().values);  // (one rank: every slot, in order)
   // per-phase breakdown of the schedule that was timed: one more solve with the same kernels, traced with events
   PhaseTimes ph;
   if (a.phases && !a.timers) {
@@ -509,6 +523,8 @@ int main(int argc, char** argv) {
       group = std::make_unique<ShmGroup>(a.prob, parse_dims(a.decomp, lworld, a.prob.N), lworld, job_segment_name(),
                                          cpu_rank);
     }
+    W3D_REQUIRE(a.receivers.empty() || (!group && lworld <= 1),
+                "--receivers / --traces: one rank only (gathering traces from several processes is not implemented)");
     const int rc = a.cpu ? (group ? run_cpu_rank(a, *group, cpu_rank) : run_cpu(a)) : run_gpu(a);
     if (rc == 3) std::fprintf(stderr, "wave3d: solution blew up (non-finite error)\n");
     return rc;

@@ -194,6 +194,13 @@ class CpuSolver {
   // values ignored; psi_global = nullptr: ψ = 0): u⁰, u¹ by cpu_first_step_field, then the ordinary steps from n = 1.
   // The error columns then are the difference from the eigenmode. It and set_state replace each other.
   void set_initial(const double* phi_global, const double* psi_global);
+  // Receivers: R global nodes (ijk: R triples, each index in 0..N; duplicates allowed) whose value every following run()
+  // reads from the stored field after the start and after every cpu_leapfrog step — the plain definition, the oracle
+  // of the GPU record kernels. R = 0 removes them. traces(): the last run()'s (K+1) × R values, row n = u^n (NaN in the
+  // rows below n0 − 1 of a resumed run).
+  void set_receivers(const i64* ijk, int R);
+  const std::vector<double>& traces() const { return traces_; }
+  int receivers() const { return static_cast<int>(recv_off_.size()); }
   // E^{K−1/2} of the last run()'s u^{K−1}, u^K (which = 0), or E^{1/2} of its u⁰, u¹ (which = 1; after set_initial)
   double energy(int which) const;
   // the sums behind energy(which): kin, pot, abs (the error scale) and the summation depth
@@ -216,6 +223,8 @@ class CpuSolver {
   Layout init_lay_;
   std::vector<double> init_[2];
   EnergySums e_start_;                   // of u⁰, u¹ of the last run() after set_initial
+  std::vector<i64> recv_off_;            // receivers: Layout::off of each node
+  std::vector<double> traces_;           // [K + 1][R] of the last run()
   int runs_ = 0;
 };
 

@@ -17,6 +17,7 @@
 #include "wave3d/decomp.hpp"
 #include "wave3d/deep_plan.hpp"
 #include "wave3d/problem.hpp"
+#include "wave3d/schedule.hpp"
 #include "wave3d/tiling.hpp"
 
 namespace wave3d {
@@ -54,6 +55,19 @@ int energy_depth(const Layout& l);
 void launch_energy(const Layout& l, const Coeffs& c, double tau, const double* a, const double* b, Partial* partials,
                    hipStream_t stream);
 void launch_energy_reduce(const Partial* partials, int n, Partial* out, hipStream_t stream);
+
+// Receivers (kernels_record.hip; schedule.hpp Receiver / plan_receivers). `table`: `count` receivers in device memory;
+// `trace`: rows of `rtotal` doubles, row m = level u^m, a receiver's column = its `slot`.
+//   launch_record_cone   : the levels u^{n+1} .. u^{n+steps} (steps = 2..5) at every receiver of the table, recomputed
+//                          from the inputs prev = u^{n−1}, cur = u^n of a pass of `steps` steps on layout l — read on the
+//                          L1 ball of radius steps (cur) / steps − 1 (prev) around the receiver, never on or outside the
+//                          global boundary; bit-identical to `steps` cpu_leapfrog steps. Receivers on a global face get
+//                          +0.0. Needs ghosts `steps` deep on every axis the rank does not span.
+//   launch_record_gather : row n from a stored level: trace[n][slot] = field[off].
+void launch_record_cone(const Layout& l, const Coeffs& c, const double* prev, const double* cur, int n, int steps,
+                        const Receiver* table, int count, double* trace, i64 rtotal, hipStream_t stream);
+void launch_record_gather(const double* field, int n, const Receiver* table, int count, double* trace, i64 rtotal,
+                          hipStream_t stream);
 
 // Runs one leapfrog step over up to 6 boxes in a single launch. If `partials` is non-null the error vs φ·ct is reduced
 // per workgroup into partials[0 .. leapfrog_blocks()).

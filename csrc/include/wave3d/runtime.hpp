@@ -70,6 +70,13 @@ int load_dump_global(const std::string& prefix, const Problem& p, std::vector<do
 // PREFIX.phi → φ = u(·,0) and, when it exists, PREFIX.psi → ψ = u_t(·,0) (else psi is left empty): the same format and
 // the same N / tau / L / box checks as a checkpoint's dumps (refusals start with "initial:")
 void load_initial(const std::string& prefix, const Problem& p, std::vector<double>& phi, std::vector<double>& psi);
+// Receivers (--receivers FILE, --traces OUT). FILE: text, one "i j k" per line (global node indices; blank lines and
+// lines starting with # are skipped); returns the 3·R indices. OUT.bin: raw little-endian fp64, C order [K+1][R], row n
+// = u^n at the R nodes; OUT.json: {"format": "wave3d-traces-v1", "dtype", "order", "N", "K", "L" [, "box"], "tau",
+// "shape": [K+1, R], "nodes": [[i, j, k], ...]}.
+std::vector<i64> load_receivers(const std::string& path);
+void write_traces(const std::string& out, const Problem& p, const std::vector<i64>& ijk,
+                  const std::vector<double>& values);
 // PREFIX.prev / PREFIX.cur → u^{n0−1}, u^{n0}; returns n0
 int load_checkpoint(const std::string& prefix, const Problem& p, std::vector<double>& prev, std::vector<double>& cur);
 

@@ -3,6 +3,7 @@
 // (plan_links) and the bytes moved (traffic). GpuSolver (solver.hpp) allocates and launches what they say.
 #pragma once
 
+#include <array>
 #include <string>
 #include <vector>
 
@@ -213,6 +214,17 @@ struct Traffic {
   double field_bytes = 0.0, halo_bytes = 0.0;
 };
 Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool init_kernel);
+
+// Receivers: grid nodes whose value u^n is recorded for every n = 0..K. `nodes` holds R global (i, j, k) triples, each
+// index in 0..N; slot r of a trace row is node r of the list (a node listed twice fills two slots with the same values).
+// plan_receivers returns the ones inside rank_box(p, d, rank), in list order: every node belongs to exactly one rank.
+struct Receiver {
+  i64 slot;     // index in the global list
+  i64 x, y, z;  // local node
+  i64 off;      // Layout::off(x, y, z)
+};
+std::vector<Receiver> plan_receivers(const Problem& p, const Dims& d, int rank, const Layout& l,
+                                     const std::vector<std::array<i64, 3>>& nodes);
 
 // The global error log from the ranks' logs. Rank q's entry of step n is the pair xy[(q·(K+1) + n)·2 + {0, 1}] = (max
 // |e|, Σe²) over its nodes; per step of `checked`, in fixed rank order: the maximum (a NaN sticks) and Σe² summed left

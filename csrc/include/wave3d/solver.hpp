@@ -114,6 +114,25 @@ class GpuSolver {
   // log then is the difference from the eigenmode. set_state's preconditions for a start at step 1, with its messages.
   // It and set_state replace each other; either drops the captured graph.
   void set_initial(const double* phi_global, const double* psi_global);
+  // Receivers: R global grid nodes (ijk: R triples, each index in 0..N) whose value u^n every following solve records for
+  // n = 0..K, on its ordinary schedule. Every rank of a world is given the same list and records the nodes of its own
+  // box (plan_receivers). The levels of a fused unit are recomputed from the unit's inputs by k_record_cone, enqueued on
+  // s0 at the top of unit_shell (the inputs' ghosts are complete there and nothing writes them before the next unit's
+  // pass); stored levels — the start levels, a single-step unit's output — are gathered by k_record_gather. The pass
+  // kernels are untouched. With receivers the solve stores both start levels (no analytic start, no init2): rows 0 and
+  // 1 are gathered from memory. The trace buffer lives on the device and is NaN-filled at the start of every solve, so
+  // a row nothing wrote shows (after set_state at n0: the rows below n0 − 1). Nothing on the host per solve: the solve
+  // stays graph-captured and run_batch pipelined. Replaces an earlier list (R = 0: removes it and restores the default
+  // start) and drops the captured graph. Refused on the push transport, whose ghosts live in its staging, on fake_comm
+  // ranks and on the two-step deep-halo schedule, which only starts from the analytic pair.
+  void set_receivers(const i64* ijk, int R);
+  // The last solve's (K+1) × owned() values, row n = u^n (run_batch: its last solve's), and the owned receivers' slots
+  // in the global list.
+  struct Traces {
+    std::vector<double> values;
+    std::vector<i64> slots;
+  };
+  Traces traces() const;
   // Discrete energy (cpu.hpp cpu_energy): which = 0: E^{K−1/2} of the retained u^{K−1}, u^K; which = 1: E^{1/2},
   // computed inside the solve right after the first-step kernel (solves started by set_initial) and kept on the
   // device. One rank only. energy_sums: the kinetic and potential sums themselves.
@@ -164,6 +183,8 @@ class GpuSolver {
   // whether the last solve's passes stored u^{K−1} themselves (false: its last pass left it out, UnitPlan::drop_prev,
   // and the first of energy(0), download(1), field_hash(1) rebuilds it)
   bool stored_prev() const { return units_.empty() || !units_.back().drop_prev; }
+  // whether the last solve's first pass computed u⁰, u¹ itself (no init kernel; never with receivers)
+  bool analytic_start() const { return analytic_; }
 
  private:
   friend class GpuGroup;
@@ -271,6 +292,13 @@ class GpuSolver {
   bool initial_ = false;              // set_initial: runs start with k_first_step_field on init_[0] = φ, init_[1] = ψ
   Layout init_lay_;                   // ... their layout (the solve layout's box, one ghost layer more)
   double* init_[2] = {nullptr, nullptr};  // device (init_[1] null: ψ = 0)
+  bool recording_ = false;            // set_receivers with R > 0 (on every rank of a world, whatever it owns)
+  std::vector<Receiver> recv_;        // this rank's receivers; slot = the index in the GLOBAL list ...
+  Receiver* recv_dev_ = nullptr;      // ... and in device memory with slot = the column of trace_ (the index in recv_)
+  double* trace_ = nullptr;           // device: [K + 1][recv_.size()]
+  int n_recv() const { return static_cast<int>(recv_.size()); }
+  void record_stored(int n, const double* buf);  // row n from a stored level, on s0
+  void record_unit(const UnitPlan& u);           // top of unit_shell: a fused unit's levels from its inputs, on s0
   mutable Partial* energy_part_ = nullptr;  // k_energy's partials, then [n] = E^{K−1/2}'s sums, [n + 1] = E^{1/2}'s
   void energy_alloc() const;
   void drop_graphs();
@@ -404,6 +432,7 @@ class GpuGroup {
   GpuGroup& operator=(const GpuGroup&) = delete;
   RunResult run();  // global error log (rank-ordered combine), solve_s = wall time of the group solve
   GpuSolver& rank(int r) { return *ranks_[static_cast<size_t>(r)]; }
+  const Problem& problem() const { return ranks_[0]->problem(); }
   int world() const { return static_cast<int>(ranks_.size()); }
   const std::string& transport() const { return transport_; }
   bool graph_enabled() const { return multi_ ? ranks_[0]->options().graph : graph_; }
@@ -411,6 +440,10 @@ class GpuGroup {
   std::vector<int> comm_counts() const;
   void set_state(const double* prev_global, const double* cur_global, int n0);  // every rank (GpuSolver::set_state)
   void set_initial(const double* phi_global, const double* psi_global);         // every rank (GpuSolver::set_initial)
+  // every rank (GpuSolver::set_receivers); traces(): the global (K+1) × R array of the last run(), assembled from the
+  // ranks' columns
+  void set_receivers(const i64* ijk, int R);
+  std::vector<double> traces() const;
 
  private:
   void enqueue();
@@ -427,6 +460,7 @@ class GpuGroup {
   std::vector<hipEvent_t> join_;
   hipGraphExec_t exec_ = nullptr;
   bool multi_ = false;  // "multi-device": every rank on its own GPU, solved by its own thread
+  int n_recv_ = 0;      // receivers in the global list
 };
 
 // Host-scalar collectives over the RCCL communicator (timer max-reduction, barriers). Blocking.

@@ -8,6 +8,8 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <array>
+#include <cstring>
 #include <tuple>
 
 #include "wave3d/capture_guard.hpp"
@@ -34,6 +36,21 @@ double* mut_ptr(darr& a, i64 need, const char* what) {
 const double* ro_ptr(const darr& a, i64 need, const char* what) {
   W3D_REQUIRE(a.size() >= need, std::string(what) + ": array too small");
   return a.data();
+}
+
+// receivers: an (R, 3) integer array of global node indices
+using iarr = py::array_t<i64, py::array::c_style | py::array::forcecast>;
+const i64* receiver_ptr(const iarr& a, int* R) {
+  W3D_REQUIRE(a.size() == 0 || (a.ndim() == 2 && a.shape(1) == 3), "receivers: an (R, 3) integer array of node indices");
+  *R = a.size() == 0 ? 0 : static_cast<int>(a.shape(0));
+  return a.data();
+}
+std::vector<std::array<i64, 3>> receiver_nodes(const iarr& a) {
+  int R = 0;
+  const i64* p = receiver_ptr(a, &R);
+  std::vector<std::array<i64, 3>> v(static_cast<size_t>(R));
+  for (int r = 0; r < R; ++r) v[static_cast<size_t>(r)] = {p[3 * r], p[3 * r + 1], p[3 * r + 2]};
+  return v;
 }
 
 template <class T>
@@ -267,6 +284,16 @@ PYBIND11_MODULE(_C, m) {
       .def("count", &LBox::count)
       .def("as_tuple", [](const LBox& b) { return py::make_tuple(b.x0, b.x1, b.y0, b.y1, b.z0, b.z1); });
   m.def("compute_box", &compute_box);
+  m.def("plan_receivers",
+        [](const Problem& p, const Dims& d, int rank, const Layout& l, const iarr& nodes) {
+          const std::vector<Receiver> v = plan_receivers(p, d, rank, l, receiver_nodes(nodes));
+          static_assert(sizeof(Receiver) == 5 * sizeof(i64), "a Receiver is five int64s");
+          iarr out({static_cast<py::ssize_t>(v.size()), static_cast<py::ssize_t>(5)});
+          if (!v.empty()) std::memcpy(out.mutable_data(), v.data(), v.size() * sizeof(Receiver));
+          return out;
+        },
+        py::arg("problem"), py::arg("dims"), py::arg("rank"), py::arg("layout"), py::arg("nodes"),
+        "this rank's receivers of the (R, 3) global node list: int64 rows (slot, x, y, z, off)");
   m.def(
       "shell_split",
       [](const LBox& full, const std::vector<std::vector<bool>>& nbv) {
@@ -415,6 +442,17 @@ PYBIND11_MODULE(_C, m) {
         if (!psi.is_none()) psi_a = psi.cast<darr>();
         s.set_initial(ro_ptr(phi, n * n * n, "phi"), psi.is_none() ? nullptr : ro_ptr(psi_a, n * n * n, "psi"));
       }, py::arg("phi"), py::arg("psi") = py::none())
+      .def("set_receivers", [](CpuSolver& s, const iarr& nodes) {
+        int R = 0;
+        const i64* p = receiver_ptr(nodes, &R);
+        s.set_receivers(p, R);
+      }, py::arg("nodes"), "record u^n at these (R, 3) global nodes in every following run()")
+      .def("traces", [](const CpuSolver& s) {
+        const i64 R = s.receivers();
+        W3D_REQUIRE(R > 0 && !s.traces().empty(), "traces: no receivers are set, or no solve has run since");
+        return darr({static_cast<py::ssize_t>(s.traces().size() / static_cast<size_t>(R)), static_cast<py::ssize_t>(R)},
+                    s.traces().data());
+      }, "the last run()'s (K+1, R) values, row n = u^n")
       .def("energy", &CpuSolver::energy, py::arg("which") = 0);
 
   // ---------------- GPU ----------------
@@ -470,6 +508,24 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("layout"), py::arg("src"), py::arg("coeffs"), py::arg("tau"), py::arg("phi"), py::arg("psi"),
         py::arg("u0"), py::arg("u1"), py::arg("stream"), "k_first_step_field (psi = 0: no psi term)");
+  // receivers: the table is `count` rows of plan_receivers' array in device memory (a Receiver is its five int64s)
+  m.def("gpu_record_cone",
+        [](const Layout& l, const Coeffs& c, std::uintptr_t prev, std::uintptr_t cur, int n, int steps,
+           std::uintptr_t table, int count, std::uintptr_t trace, i64 rtotal, std::uintptr_t stream) {
+          launch_record_cone(l, c, dptr<const double>(prev), dptr<const double>(cur), n, steps,
+                             dptr<const Receiver>(table), count, dptr<double>(trace), rtotal, sptr(stream));
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("prev"), py::arg("cur"), py::arg("n"), py::arg("steps"),
+        py::arg("table"), py::arg("count"), py::arg("trace"), py::arg("rtotal"), py::arg("stream"),
+        "k_record_cone: rows n+1 .. n+steps of trace from the pass inputs prev = u^{n-1}, cur = u^n");
+  m.def("gpu_record_gather",
+        [](std::uintptr_t field, int n, std::uintptr_t table, int count, std::uintptr_t trace, i64 rtotal,
+           std::uintptr_t stream) {
+          launch_record_gather(dptr<const double>(field), n, dptr<const Receiver>(table), count, dptr<double>(trace),
+                               rtotal, sptr(stream));
+        },
+        py::arg("field"), py::arg("n"), py::arg("table"), py::arg("count"), py::arg("trace"), py::arg("rtotal"),
+        py::arg("stream"), "k_record_gather: row n of trace from a stored level");
   m.def("gpu_energy_depth", &energy_depth, "depth D of k_energy's reduction tree for this layout");
   m.def("gpu_energy_partials", &energy_partials);
   m.def("gpu_energy",
@@ -772,6 +828,19 @@ PYBIND11_MODULE(_C, m) {
         if (!psi.is_none()) psi_a = psi.cast<darr>();
         s.set_initial(ro_ptr(phi, n * n * n, "phi"), psi.is_none() ? nullptr : ro_ptr(psi_a, n * n * n, "psi"));
       }, py::arg("phi"), py::arg("psi") = py::none())
+      .def("set_receivers", [](GpuSolver& s, const iarr& nodes) {
+        int R = 0;
+        const i64* p = receiver_ptr(nodes, &R);
+        s.set_receivers(p, R);
+      }, py::arg("nodes"), "record u^n at these (R, 3) global nodes in every following solve (this rank: the ones it owns)")
+      .def("traces", [](const GpuSolver& s) {
+        const GpuSolver::Traces t = s.traces();
+        const py::ssize_t own = static_cast<py::ssize_t>(t.slots.size());
+        darr v({static_cast<py::ssize_t>(s.problem().K + 1), own});
+        if (own > 0) std::memcpy(v.mutable_data(), t.values.data(), t.values.size() * sizeof(double));
+        return py::make_tuple(v, t.slots);
+      }, "the last solve's ((K+1, owned) values, the owned receivers' slots in the list)")
+      .def_property_readonly("analytic_start", &GpuSolver::analytic_start)
       .def("energy", &GpuSolver::energy, py::arg("which") = 0,
            "discrete energy E^{K-1/2} (which = 0) / E^{1/2} (which = 1, after set_initial); one rank only")
       .def("energy_sums", [](const GpuSolver& s, int which) {
@@ -867,6 +936,16 @@ PYBIND11_MODULE(_C, m) {
         if (!psi.is_none()) psi_a = psi.cast<darr>();
         g.set_initial(ro_ptr(phi, n * n * n, "phi"), psi.is_none() ? nullptr : ro_ptr(psi_a, n * n * n, "psi"));
       }, py::arg("phi"), py::arg("psi") = py::none())
+      .def("set_receivers", [](GpuGroup& g, const iarr& nodes) {
+        int R = 0;
+        const i64* p = receiver_ptr(nodes, &R);
+        g.set_receivers(p, R);
+      }, py::arg("nodes"))
+      .def("traces", [](const GpuGroup& g) {
+        const std::vector<double> t = g.traces();
+        const py::ssize_t rows = static_cast<py::ssize_t>(g.problem().K + 1);
+        return darr({rows, static_cast<py::ssize_t>(t.size()) / rows}, t.data());
+      }, "the last run()'s global (K+1, R) values, assembled from the ranks")
       .def_property_readonly("transport", &GpuGroup::transport)
       .def_property_readonly("graph_enabled", &GpuGroup::graph_enabled)
       .def_property_readonly("world", &GpuGroup::world);

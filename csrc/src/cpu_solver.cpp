@@ -106,6 +106,20 @@ void CpuSolver::set_state(const double* prev, const double* cur, int n0) {
   resume_n_ = n0;
 }
 
+void CpuSolver::set_receivers(const i64* ijk, int R) {
+  W3D_REQUIRE(R >= 0 && (R == 0 || ijk != nullptr), "set_receivers: bad receiver list");
+  std::vector<i64> off;
+  for (int r = 0; r < R; ++r) {
+    const i64 i = ijk[3 * r], j = ijk[3 * r + 1], k = ijk[3 * r + 2];
+    W3D_REQUIRE(i >= 0 && i <= prob_.N && j >= 0 && j <= prob_.N && k >= 0 && k <= prob_.N,
+                "receiver " + std::to_string(r) + " = (" + std::to_string(i) + ", " + std::to_string(j) + ", " +
+                    std::to_string(k) + ") is outside the grid 0.." + std::to_string(prob_.N));
+    off.push_back(lay_.off(i, j, k));
+  }
+  recv_off_ = std::move(off);
+  traces_.clear();
+}
+
 std::vector<int> CpuSolver::check_steps() const {
   std::vector<int> v;
   for (int n = 1; n <= prob_.K; ++n)
@@ -140,6 +154,15 @@ CpuResult CpuSolver::run() {
   } else {
     cpu_init_first(lay_, c, s, u_[0].data(), u_[1].data());
   }
+  const size_t nrec = recv_off_.size();
+  auto trace_row = [&](int n, const std::vector<double>& u) {
+    for (size_t k = 0; k < nrec; ++k) traces_[static_cast<size_t>(n) * nrec + k] = u[static_cast<size_t>(recv_off_[k])];
+  };
+  if (nrec > 0) {
+    traces_.assign(static_cast<size_t>(prob_.K + 1) * nrec, std::nan(""));
+    trace_row(n_start - 1, u_[0]);
+    trace_row(n_start, u_[1]);
+  }
   const double t1 = now_s();
   r.init_s = t1 - t0;
   if (is_check[1] && resume_n_ == 0) {
@@ -159,6 +182,7 @@ CpuResult CpuSolver::run() {
     }
     r.compute_s += now_s() - tc;
     std::swap(cur, old);
+    if (nrec > 0) trace_row(n + 1, u_[cur]);
   }
   final_ = cur;
   ++runs_;

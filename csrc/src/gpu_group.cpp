@@ -131,6 +131,36 @@ void GpuGroup::set_initial(const double* phi, const double* psi) {
   graph_ = graph0_;
 }
 
+void GpuGroup::set_receivers(const i64* ijk, int R) {
+  for (auto& r : ranks_) {
+    DeviceScope scope(r->device());
+    r->set_receivers(ijk, R);
+  }
+  n_recv_ = R;
+  if (multi_) return;  // (every rank captures its own solve)
+  if (exec_) W3D_HIP(hipGraphExecDestroy(exec_));
+  exec_ = nullptr;  // (graph_ stays as it is: the record launches are device work like any other)
+}
+
+std::vector<double> GpuGroup::traces() const {
+  W3D_REQUIRE(n_recv_ > 0, "traces: no receivers are set (set_receivers)");
+  const size_t rows = static_cast<size_t>(ranks_[0]->sch_.prob.K + 1), R = static_cast<size_t>(n_recv_);
+  std::vector<double> all(rows * R);
+  std::vector<char> seen(R, 0);
+  for (const auto& r : ranks_) {
+    const GpuSolver::Traces t = r->traces();
+    const size_t own = t.slots.size();
+    for (size_t k = 0; k < own; ++k) {
+      const size_t slot = static_cast<size_t>(t.slots[k]);
+      W3D_REQUIRE(slot < R && !seen[slot], "traces: a receiver is owned by two ranks");
+      seen[slot] = 1;
+      for (size_t n = 0; n < rows; ++n) all[n * R + slot] = t.values[n * own + k];
+    }
+  }
+  for (char s : seen) W3D_REQUIRE(s, "traces: a receiver is owned by no rank");
+  return all;
+}
+
 std::vector<int> GpuGroup::comm_counts() const {
   std::vector<int> v;
   for (const auto& r : ranks_)

@@ -1,6 +1,7 @@
 // Field dumps and checkpoints of the native runtime: wave3d-dump-v1 (SURVEY.md §5.9 — the reference writes no field
 // at all, report.pdf / readme.md have only stdout). See wave3d/runtime.hpp.
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -121,6 +122,43 @@ int load_dump_global(const std::string& prefix, const Problem& p, std::vector<do
     W3D_REQUIRE(static_cast<bool>(f), what + ": short file " + b + ".bin");
   }
   return step;
+}
+
+std::vector<i64> load_receivers(const std::string& path) {
+  std::ifstream f(path);
+  W3D_REQUIRE(static_cast<bool>(f), "receivers: cannot read " + path);
+  std::vector<i64> ijk;
+  std::string line;
+  for (int no = 1; std::getline(f, line); ++no) {
+    const size_t b = line.find_first_not_of(" \t\r");
+    if (b == std::string::npos || line[b] == '#') continue;
+    long long i = 0, j = 0, k = 0;
+    char extra = 0;
+    W3D_REQUIRE(std::sscanf(line.c_str(), "%lld %lld %lld %c", &i, &j, &k, &extra) == 3,
+                "receivers: " + path + " line " + std::to_string(no) + ": expected three integers i j k");
+    ijk.insert(ijk.end(), {static_cast<i64>(i), static_cast<i64>(j), static_cast<i64>(k)});
+  }
+  W3D_REQUIRE(!ijk.empty(), "receivers: " + path + " lists no node");
+  return ijk;
+}
+
+void write_traces(const std::string& out, const Problem& p, const std::vector<i64>& ijk,
+                  const std::vector<double>& values) {
+  const size_t R = ijk.size() / 3, rows = static_cast<size_t>(p.K + 1);
+  W3D_REQUIRE(values.size() == rows * R, "traces: " + std::to_string(values.size()) + " values for " +
+                                             std::to_string(rows) + " x " + std::to_string(R));
+  std::ofstream f(out + ".bin", std::ios::binary | std::ios::trunc);
+  f.write(reinterpret_cast<const char*>(values.data()), static_cast<std::streamsize>(values.size() * sizeof(double)));
+  W3D_REQUIRE(static_cast<bool>(f), "traces: cannot write " + out + ".bin");
+  std::ofstream j(out + ".json", std::ios::trunc);
+  j.precision(17);
+  j << "{\"format\": \"wave3d-traces-v1\", \"dtype\": \"float64\", \"order\": \"C\", \"N\": " << p.N << ", \"K\": " << p.K
+    << ", \"L\": " << p.L;
+  if (p.is_box()) j << ", \"box\": [" << p.L << ", " << p.edge_y() << ", " << p.edge_z() << "]";
+  j << ", \"tau\": " << p.tau << ", \"shape\": [" << rows << ", " << R << "], \"nodes\": [";
+  for (size_t r = 0; r < R; ++r)
+    j << (r ? ", [" : "[") << ijk[3 * r] << ", " << ijk[3 * r + 1] << ", " << ijk[3 * r + 2] << "]";
+  j << "]}\n";
 }
 
 // --resume PREFIX: u^{n0−1} from PREFIX.prev, u^{n0} from PREFIX.cur; returns n0

@@ -383,6 +383,24 @@ Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool 
   return t;
 }
 
+std::vector<Receiver> plan_receivers(const Problem& p, const Dims& d, int rank, const Layout& l,
+                                     const std::vector<std::array<i64, 3>>& nodes) {
+  const Box b = rank_box(p, d, rank);
+  W3D_REQUIRE(l.gx0 == b.x0 && l.gy0 == b.y0 && l.gz0 == b.z0 && l.nx == b.nx() && l.ny == b.ny() && l.nz == b.nz(),
+              "plan_receivers: the layout is not this rank's");
+  std::vector<Receiver> v;
+  for (size_t r = 0; r < nodes.size(); ++r) {
+    const i64 i = nodes[r][0], j = nodes[r][1], k = nodes[r][2];
+    W3D_REQUIRE(i >= 0 && i <= p.N && j >= 0 && j <= p.N && k >= 0 && k <= p.N,
+                "receiver " + std::to_string(r) + " = (" + std::to_string(i) + ", " + std::to_string(j) + ", " +
+                    std::to_string(k) + ") is outside the grid 0.." + std::to_string(p.N));
+    if (i < b.x0 || i >= b.x1 || j < b.y0 || j >= b.y1 || k < b.z0 || k >= b.z1) continue;
+    const i64 x = i - b.x0, y = j - b.y0, z = k - b.z0;
+    v.push_back(Receiver{static_cast<i64>(r), x, y, z, l.off(x, y, z)});
+  }
+  return v;
+}
+
 ErrorLog combine_error_log(const double* xy, int nsrc, int K, int N, const std::vector<int>& checked) {
   ErrorLog r;
   const size_t per = static_cast<size_t>(K + 1);

@@ -173,6 +173,8 @@ GpuSolver::~GpuSolver() {
   for (double* p : {u_[0], u_[1], u_[2], u_[3], d_s_, send_buf_, recv_buf_, init_[0], init_[1]})
     if (p) (void)hipFree(p);
   if (energy_part_) (void)hipFree(energy_part_);
+  if (recv_dev_) (void)hipFree(recv_dev_);
+  if (trace_) (void)hipFree(trace_);
   if (partials_) (void)hipFree(partials_);
   if (tb_partials_) (void)hipFree(tb_partials_);
   if (errlog_) (void)hipFree(errlog_);
@@ -200,7 +202,8 @@ size_t GpuSolver::device_bytes() const {
          recv_bytes_ + send_bytes_ + static_cast<size_t>(n_partials_) * sizeof(Partial) +
          static_cast<size_t>(sch_.prob.N + 3) * sizeof(double) + tb_bytes_ +
          ((init_[0] ? 1u : 0u) + (init_[1] ? 1u : 0u)) * static_cast<size_t>(init_lay_.bytes()) +
-         (energy_part_ ? static_cast<size_t>(energy_partials(sch_.lay) + 2) * sizeof(Partial) : 0u);
+         (energy_part_ ? static_cast<size_t>(energy_partials(sch_.lay) + 2) * sizeof(Partial) : 0u) +
+         recv_.size() * (sizeof(Receiver) + static_cast<size_t>(sch_.prob.K + 1) * sizeof(double));
 }
 
 void GpuSolver::drop_graphs() {
@@ -243,6 +246,57 @@ void GpuSolver::set_initial(const double* phi, const double* psi) {
   resume_n_ = 0;
   resume_[0] = std::vector<double>();
   resume_[1] = std::vector<double>();
+}
+
+void GpuSolver::set_receivers(const i64* ijk, int R) {
+  W3D_REQUIRE(R >= 0 && (R == 0 || ijk != nullptr), "set_receivers: bad receiver list");
+  if (R > 0) {
+    W3D_REQUIRE(!sch_.push, "receivers: not on the push transport (its ghost planes live in the staging buffers, which "
+                            "the record kernel does not read); use rccl or sdma");
+    W3D_REQUIRE(!sch_.opt.fake_comm, "receivers: a fake rank's ghosts are never delivered");
+    W3D_REQUIRE(sch_.mode != Mode::kDeep, "receivers: the two-step deep-halo passes start from the analytic pair only; "
+                                          "use the LDS passes or temporal = 1");
+  }
+  std::vector<std::array<i64, 3>> nodes(static_cast<size_t>(R));
+  for (int r = 0; r < R; ++r) nodes[static_cast<size_t>(r)] = {ijk[3 * r], ijk[3 * r + 1], ijk[3 * r + 2]};
+  std::vector<Receiver> mine = plan_receivers(sch_.prob, sch_.dims, sch_.rank, sch_.lay, nodes);  // (refuses bad nodes)
+  DeviceScope scope(dev_, true);
+  drop_graphs();
+  if (recv_dev_) W3D_HIP(hipFree(recv_dev_));
+  if (trace_) W3D_HIP(hipFree(trace_));
+  recv_dev_ = nullptr;
+  trace_ = nullptr;
+  recv_ = std::move(mine);
+  recording_ = R > 0;
+  if (recv_.empty()) return;
+  std::vector<Receiver> cols = recv_;
+  for (size_t k = 0; k < cols.size(); ++k) cols[k].slot = static_cast<i64>(k);
+  const size_t tbytes = static_cast<size_t>(sch_.prob.K + 1) * recv_.size() * sizeof(double);
+  W3D_HIP(hipMalloc(&recv_dev_, cols.size() * sizeof(Receiver)));
+  W3D_HIP(hipMemcpy(recv_dev_, cols.data(), cols.size() * sizeof(Receiver), hipMemcpyHostToDevice));
+  W3D_HIP(hipMalloc(&trace_, tbytes));
+  W3D_HIP(hipMemset(trace_, 0xFF, tbytes));  // (NaN until a solve writes it)
+}
+
+GpuSolver::Traces GpuSolver::traces() const {
+  W3D_REQUIRE(recording_, "traces: no receivers are set (set_receivers)");
+  Traces t;
+  for (const Receiver& r : recv_) t.slots.push_back(r.slot);
+  t.values.resize(static_cast<size_t>(sch_.prob.K + 1) * recv_.size());
+  if (recv_.empty()) return t;
+  DeviceScope scope(dev_, true);
+  W3D_HIP(hipMemcpy(t.values.data(), trace_, t.values.size() * sizeof(double), hipMemcpyDeviceToHost));
+  return t;
+}
+
+void GpuSolver::record_stored(int n, const double* buf) {
+  if (recv_.empty()) return;
+  launch_record_gather(buf, n, recv_dev_, n_recv(), trace_, n_recv(), s0_);
+}
+
+void GpuSolver::record_unit(const UnitPlan& u) {
+  if (recv_.empty() || !u.fused()) return;
+  launch_record_cone(sch_.lay, coef_, u_[old_], u_[cur_], u.n, u.steps, recv_dev_, n_recv(), trace_, n_recv(), s0_);
 }
 
 Partial GpuSolver::energy_sums(int which) const {
@@ -328,9 +382,12 @@ void GpuSolver::phase_init() {
   if (sch_.sdma || sch_.push || resume_n_ > 0)
     W3D_HIP(hipMemsetAsync(errlog_, 0, static_cast<size_t>(K + 1) * sizeof(Partial), s0_));
   if (sch_.push) push_begin_solve();
+  // (receivers: NaN in every row until this solve writes it)
+  if (trace_)
+    W3D_HIP(hipMemsetAsync(trace_, 0xFF, static_cast<size_t>(K + 1) * recv_.size() * sizeof(double), s0_));
   // one rank on the LDS kernel: the first pass starts from the analytic u⁰, u¹ itself (no init kernel, no reads)
   analytic_ = (sch_.mode == Mode::kFusedSingle || sch_.mode == Mode::kDeepTb) && sch_.analytic_ok() && resume_n_ == 0 &&
-              !initial_;
+              !initial_ && !recording_;  // (receivers: both start levels are stored, rows 0 and 1 are gathered)
   if (resume_n_ > 0) {  // loaded state: u^{n0−1} → buf 0, u^{n0} → buf 1 (ghosts included)
     const size_t bytes = static_cast<size_t>(sch_.lay.bytes());
     timed(kPhaseInit, s0_, [&] {
@@ -353,7 +410,7 @@ void GpuSolver::phase_init() {
     start_n_ = 1;
   } else if (analytic_) {
     start_n_ = 1;
-  } else if (sch_.opt.init2 && K >= 2) {
+  } else if (sch_.opt.init2 && K >= 2 && !recording_) {
     // u¹ -> buf 0, u² -> buf 1 analytically (no read pass), ghosts included; the first leapfrog step is n = 2
     timed(kPhaseInit, s0_, [&] {
       launch_init_two(sch_.lay, coef_, s, u_[0], u_[1], ct_[2], is_check_[2] ? partials_ : nullptr, s0_);
@@ -367,6 +424,12 @@ void GpuSolver::phase_init() {
     timed(kPhaseInit, s0_, [&] { launch_init_first(sch_.lay, coef_, s, u_[0], u_[1], s0_); });
     timed(kPhaseCheck, s0_, [&] { check_stored(1, u_[1]); });
     start_n_ = 1;
+  }
+  if (recording_) {  // (every start above but init2 left u^{start−1} in buffer 0 and u^{start} in buffer 1)
+    timed(kPhaseCheck, s0_, [&] {
+      record_stored(start_n_ - 1, u_[0]);
+      record_stored(start_n_, u_[1]);
+    });
   }
   cur_ = 1;
   old_ = 0;
@@ -392,6 +455,9 @@ void GpuSolver::unit_shell(int i) {
   // (s0: every pass of the unit follows it there — the shells on the side stream wait for ev_shell_, recorded below —
   // and the previous unit's passes, which read that plane of the same buffer as a ghost, precede it)
   if (sch_.opt.poison_ghosts && u.ghost_bits) poison(u, uf_, s0_, true);
+  // receivers: the unit's levels from its inputs, whose ghosts are complete here (the previous unit's exchange has been
+  // joined into s0) and which nothing writes before the next unit's pass
+  if (recording_ && u.fused()) timed(kPhaseCheck, s0_, [&] { record_unit(u); });
   const int nc = u.n + u.steps;
   const bool chk = is_check_[static_cast<size_t>(nc)] != 0;
   if (sch_.mode == Mode::kDeep) {
@@ -639,6 +705,8 @@ void GpuSolver::unit_interior(int i) {
   }
   if (wait && !joined) capture::wait(s0_, ev_halo_);
   if (chk && np > 0) timed(kPhaseCheck, s0_, [&] { launch_reduce(partials_, np, errlog_ + nc, s0_); });
+  // receivers: a single step's new level, stored in place over u^{n−1} (owned nodes only: no ghost is read)
+  if (recording_ && !u.fused()) timed(kPhaseCheck, s0_, [&] { record_stored(nc, u_[old_]); });
   if (sch_.opt.debug_sync) W3D_HIP(hipDeviceSynchronize());
   last_in_[0] = old_;
   last_in_[1] = cur_;

@@ -54,6 +54,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "from PREFIX.psi (backends hip and cpu)")
     ap.add_argument("--energy", action="store_true",
                     help="print the discrete energy E(1/2), E(K-1/2) and its drift (with --initial)")
+    ap.add_argument("--receivers", default="", metavar="FILE",
+                    help="record u at grid nodes for every step 0..K: FILE lists one node per line as i j k")
+    ap.add_argument("--traces", default="", metavar="OUT",
+                    help="write the recorded (K+1) x R values to OUT.bin / OUT.json (utils/dump.py load_traces)")
     ap.add_argument("--force", action="store_true", help="run even if the CFL condition is violated")
     ap.add_argument("--quiet", action="store_true")
     return ap
@@ -79,6 +83,8 @@ def main(argv=None) -> int:
         ap.error("--initial and --resume exclude each other")
     if a.energy and not a.initial:
         ap.error("--energy needs --initial (E(1/2) is kept by solves that start from it)")
+    if bool(a.receivers) != bool(a.traces):
+        ap.error("--receivers FILE and --traces OUT go together")
     import torch
     import torch.distributed as dist
 
@@ -144,6 +150,14 @@ def main(argv=None) -> int:
                 return 2
             fields.append(f)
         s.set_initial(*fields)
+    nodes = None
+    if a.receivers:
+        if world > 1:
+            print("wave3d: --receivers / --traces: one rank (or --world P in this process) only; gathering traces from "
+                  "several processes is not implemented", file=sys.stderr)
+            return 2
+        nodes = dumpio.load_receivers(a.receivers)
+        s.set_receivers(nodes)
     r = None
     times = []
     for i in range(a.warmup + a.repeat):
@@ -178,6 +192,8 @@ def main(argv=None) -> int:
                            "gcell_per_s": gcell_per_s(a.N, a.K, best),
                            **({"energy_start": e_start, "energy_end": e_end} if a.energy else {}),
                            "steps": [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]}, f)
+    if a.traces:
+        dumpio.save_traces(a.traces, s.traces().numpy(), nodes, N=a.N, K=a.K, L=a.L, tau=a.tau, box=spec.edges)
     if a.dump or a.checkpoint:
         def write(prefix, which):
             if s.transport in ("loopback", "rccl-self", "push", "sdma"):

@@ -380,6 +380,47 @@ class Solver:
         self._initial = (to_np(phi), None if psi is None else to_np(psi))
         self._impl.set_initial(*self._initial)
 
+    def set_receivers(self, nodes) -> None:
+        """Receivers: record u^n at chosen grid nodes for every step n = 0..K of every following run(). ``nodes`` is an
+        (R, 3) integer array of GLOBAL node indices (i, j, k), each in 0..N; a node may be listed twice (two equal
+        columns). An empty list removes them. The HIP backend keeps its schedule — fused passes, hipGraph, run_batch,
+        in-process groups: the levels a fused pass never stores are recomputed from its inputs by ``k_record_cone``
+        — except that the start stores u⁰ and u¹ (no analytic start). Backends hip (one rank in process, or an
+        in-process group) and cpu; not the push transport."""
+        import numpy as np
+
+        if self.runtime == "process":
+            raise NotImplementedError("receivers: runtime='process' is out of scope (traces are not gathered from "
+                                      "rank processes); run in process, or use bin/wave3d --receivers / --traces")
+        C = load()
+        native = isinstance(self._impl, (C.GpuGroup, C.CpuSolver)) or (isinstance(self._impl, C.GpuSolver)
+                                                                        and self.world == 1)
+        if not native:
+            raise NotImplementedError("receivers need the native cpu backend, one hip rank, or an in-process hip "
+                                      "group (gathering traces from several processes is out of scope)")
+        a = np.asarray(nodes.cpu().numpy() if isinstance(nodes, torch.Tensor) else nodes)
+        if a.size and (a.ndim != 2 or a.shape[1] != 3):
+            raise ValueError(f"set_receivers: expected an (R, 3) array of node indices, got shape {a.shape}")
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("set_receivers: node indices are integers")
+        a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1, 3)
+        self._impl.set_receivers(a)
+        self._receivers = a.shape[0]
+
+    def traces(self) -> torch.Tensor:
+        """The last run()'s recorded values: a (K+1, R) float64 CPU tensor, row n = u^n at the R receivers in the order
+        ``set_receivers`` got them (run_batch: its last solve's). Rows below step − 1 of a ``set_state`` start are NaN."""
+        import numpy as np
+
+        if self.runtime == "process":
+            raise NotImplementedError("receivers: runtime='process' is out of scope")
+        if not getattr(self, "_receivers", 0):
+            raise ValueError("traces: no receivers are set (set_receivers)")
+        t = self._impl.traces()
+        if isinstance(t, tuple):  # one hip rank: (values, slots); it owns every slot, in order
+            t = t[0]
+        return torch.from_numpy(np.array(t, dtype=np.float64).reshape(self.spec.K + 1, self._receivers))
+
     def energy(self, which: int = 0) -> float:
         """Discrete energy of the last run(): ``which=0`` E^{K−1/2} from the retained u^{K−1}, u^K; ``which=1``
         E^{1/2} from u⁰, u¹ (after ``set_initial``). Leapfrog conserves it exactly in exact arithmetic (cpu.hpp

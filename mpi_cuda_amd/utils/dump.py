@@ -62,6 +62,55 @@ def box_of(meta: dict) -> tuple[float, float, float]:
     return tuple(float(e) for e in b) if b else (float(meta["L"]),) * 3
 
 
+TRACES_FORMAT = "wave3d-traces-v1"
+
+
+def save_traces(prefix: str, traces: np.ndarray, nodes, *, N: int, K: int, L: float, tau: float, box=None) -> None:
+    """Receiver traces (``Solver.traces()``, ``--traces``): ``<prefix>.bin`` raw little-endian float64, C order
+    [K+1][R], row n = u^n at the R nodes; ``<prefix>.json`` {"format": "wave3d-traces-v1", "dtype", "order", "N", "K",
+    "L" [, "box"], "tau", "shape": [K+1, R], "nodes": [[i, j, k], ...]}. The native CLI writes the same files."""
+    traces = np.ascontiguousarray(traces, dtype="<f8")
+    nodes = [[int(v) for v in n] for n in nodes]
+    if traces.shape != (K + 1, len(nodes)):
+        raise ValueError(f"traces of shape {traces.shape} for K = {K} and {len(nodes)} nodes")
+    traces.tofile(prefix + ".bin")
+    meta = {"format": TRACES_FORMAT, "dtype": "float64", "order": "C", "N": int(N), "K": int(K), "L": float(L),
+            "tau": float(tau), "shape": list(traces.shape), "nodes": nodes}
+    if box is not None and not (box[0] == box[1] == box[2]):
+        meta["box"] = [float(e) for e in box]
+    with open(prefix + ".json", "w") as f:
+        json.dump(meta, f)
+
+
+def load_traces(prefix: str) -> tuple[np.ndarray, dict]:
+    """(traces (K+1, R), sidecar) of a ``--traces`` / ``save_traces`` output; meta["nodes"] lists the R nodes."""
+    with open(prefix + ".json") as f:
+        m = json.load(f)
+    if m.get("format") != TRACES_FORMAT:
+        raise ValueError(f"{prefix}.json: not a {TRACES_FORMAT} file")
+    shape = m["shape"]
+    a = np.fromfile(prefix + ".bin", dtype="<f8")
+    if len(shape) != 2 or a.size != shape[0] * shape[1] or shape[0] != m["K"] + 1 or shape[1] != len(m["nodes"]):
+        raise ValueError(f"{prefix}.bin: size {a.size} does not match shape {shape}, K and the node list")
+    return a.reshape(shape), m
+
+
+def load_receivers(path: str) -> np.ndarray:
+    """(R, 3) int64 node indices of a ``--receivers`` file: one ``i j k`` per line, blank and # lines skipped."""
+    rows = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            if len(t) != 3:
+                raise ValueError(f"receivers: {path} line {no}: expected three integers i j k")
+            rows.append([int(v) for v in t])
+    if not rows:
+        raise ValueError(f"receivers: {path} lists no node")
+    return np.array(rows, dtype=np.int64)
+
+
 def load(prefix: str) -> tuple[np.ndarray, dict]:
     """Assemble the global field from a single- or multi-rank dump. Returns (array (N+1)³, metadata of rank 0)."""
     metas = read_meta(prefix)

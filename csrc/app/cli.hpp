@@ -65,6 +65,7 @@ struct Args {
   std::string json, dump, trace, checkpoint, resume;
   std::string initial;  // --initial PREFIX: solve from PREFIX.phi (u(.,0)) and, if present, PREFIX.psi (u_t(.,0))
   std::string receivers;  // --receivers FILE: record u^n at the listed grid nodes ("i j k" per line), n = 0..K
+  std::string sources;    // --sources FILE: point sources ("i j k f0 t0 amp" per line, a Ricker wavelet each)
   std::string traces;     // --traces OUT: write them as OUT.bin / OUT.json (wave3d-traces-v1)
   bool energy = false;  // --energy: print the discrete energy at steps 1/2 and K-1/2 and its drift
   bool quiet = false;

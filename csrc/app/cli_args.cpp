@@ -112,6 +112,10 @@ constexpr Personality kPersonalities[] = {
                "  --receivers FILE   record u at grid nodes for every step 0..K: FILE lists one node per line as i j k\n"
                "                     (indices 0..N); the solve keeps its schedule (one GPU rank, --group, or --cpu)\n"
                "  --traces OUT       write the recorded (K+1) x R values as OUT.bin (fp64, C order) + OUT.json\n"
+               "  --sources FILE     point sources w(t) delta(x - x_s): FILE lists one source per line as i j k f0 t0 amp\n"
+               "                     (a node strictly inside the grid; a Ricker wavelet of peak frequency f0 centred at\n"
+               "                     t0). The error lines then have no meaning. One GPU rank, --group (loopback,\n"
+               "                     rccl-self) or --cpu; combines with --receivers, --box, --initial; not with --resume\n"
                "  --force            run even if the CFL condition is violated\n"
                "  --quiet            only the summary\n");
   std::exit(2);
@@ -202,6 +206,7 @@ Args parse(int argc, char** argv) {
     else if (s == "--initial") a.initial = next();
     else if (s == "--receivers") a.receivers = next();
     else if (s == "--traces") a.traces = next();
+    else if (s == "--sources") a.sources = next();
     else if (s == "--energy") a.energy = true;
     else if (s == "--box") {
       const std::string v = next();  // LX,LY,LZ
@@ -258,6 +263,10 @@ Args parse(int argc, char** argv) {
   if (!a.receivers.empty() && a.np > 1)
     usage("--receivers / --traces: one rank only (gathering traces from several processes is not implemented)");
   if (!a.receivers.empty() && (a.serve || a.fake_rank >= 0)) usage("--receivers: not with --serve or --fake-rank");
+  if (!a.sources.empty() && !a.resume.empty()) usage("--sources and --resume exclude each other");
+  if (!a.sources.empty() && a.np > 1)
+    usage("--sources: one rank only (ranks of a multi-process world are not supported)");
+  if (!a.sources.empty() && (a.serve || a.fake_rank >= 0)) usage("--sources: not with --serve or --fake-rank");
   if (a.repeat < 1) a.repeat = 1;
   return a;
 }

@@ -28,6 +28,12 @@ int run_cpu(const Args& a) {
     nodes = load_receivers(a.receivers);
     s.set_receivers(nodes.data(), static_cast<int>(nodes.size() / 3));
   }
+  if (!a.sources.empty()) {
+    std::vector<i64> src;
+    std::vector<double> w;
+    const int Q = load_sources(a.sources, a.prob, src, w);
+    s.set_sources(src.data(), Q, w.data());
+  }
   if (a.serve) {  // (the rank-process protocol on the CPU solver: run / dump / quit — cli.hpp serve_loop)
     const std::string greeting = "{\"ready\": true, \"backend\": \"cpu\", \"rank\": 0, \"world\": 1, \"dims\": [1, 1, 1], "
                                  "\"schedule\": \"cpu-openmp\", \"mode\": \"cpu\", \"transport\": \"none\"}";
@@ -84,6 +90,7 @@ int run_cpu(const Args& a) {
       << ", \"phases_slowest_rank_s\": {\"init\": " << jnum(rb.init_s) << ", \"compute\": " << jnum(rb.compute_s)
       << ", \"boundary\": " << jnum(rb.boundary_s) << ", \"exchange\": " << jnum(rb.exchange_s) << "}"
       << (a.energy ? energy_json(e_start, e_end) : std::string())
+      << (a.sources.empty() ? std::string() : ", \"sources\": " + std::to_string(s.sources()))
       << ", \"steps\": " << steps_json(r.steps, r.max_err, r.rms_err) << "}\n";
   }
   if (!a.dump.empty()) write_dump(a.dump, a.prob, s.layout(), s.field(0), 0, 1, Dims{1, 1, 1});

@@ -127,6 +127,12 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
     nodes = load_receivers(a.receivers);
     g.set_receivers(nodes.data(), static_cast<int>(nodes.size() / 3));
   }
+  if (!a.sources.empty()) {
+    std::vector<i64> src;
+    std::vector<double> w;
+    const int Q = load_sources(a.sources, a.prob, src, w);
+    g.set_sources(src.data(), Q, w.data());
+  }
   if (a.serve) {
     // --group P --serve: all P ranks in this process (the Python Solver(world=P, runtime="process") of ONE Python
     // process); run / hash (summed over the ranks) / traffic (summed) / dump (one file per rank) / quit
@@ -200,7 +206,9 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
     j << "{\"backend\": \"hip\", \"group\": " << a.group << box_json(a.prob) << ", \"transport\": " << jstr(a.group_transport)
       << ", \"graph\": " << (g.graph_enabled() ? "true" : "false") << ", \"schedule\": " << jstr(g.rank(0).mode())
       << ", \"temporal\": " << g.rank(0).options().temporal << ", \"stored_prev\": "
-      << (g.rank(0).stored_prev() ? "true" : "false") << ", \"rccl_comms\": " << cc.size() << ", \"solve_s\": " << jnum(best) << ", \"steps\": [";
+      << (g.rank(0).stored_prev() ? "true" : "false") << ", \"rccl_comms\": " << cc.size() << ", \"solve_s\": " << jnum(best);
+    if (!a.sources.empty()) j << ", \"sources\": " << g.sources();
+    j << ", \"steps\": [";
     for (size_t i = 0; i < r.steps.size(); ++i)
       j << (i ? ", " : "") << "[" << r.steps[i] << ", " << jnum(r.max_err[i]) << ", " << jnum(r.rms_err[i]) << "]";
     j << "]}\n";
@@ -295,6 +303,13 @@ int run_gpu(const Args& a) {
                             "implemented)");
     nodes = load_receivers(a.receivers);
     s->set_receivers(nodes.data(), static_cast<int>(nodes.size() / 3));
+  }
+  if (!a.sources.empty()) {
+    W3D_REQUIRE(world == 1, "sources: one rank only (ranks of a multi-process world are not supported)");
+    std::vector<i64> src;
+    std::vector<double> w;
+    const int Q = load_sources(a.sources, a.prob, src, w);
+    s->set_sources(src.data(), Q, w.data());
   }
   if (a.serve) {
     const int rc = serve(a, *s, hc, file_coll, sched);
@@ -460,6 +475,7 @@ int run_gpu(const Args& a) {
           << jnum(pp.comm_ms) << ", \"check\": " << jnum(pp.check_ms) << ", \"gather\": " << jnum(pp.gather_ms)
           << "}";
       if (a.energy) j << energy_json(e_start, e_end);
+      if (!a.sources.empty()) j << ", \"sources\": " << s->sources();
       j << ", \"solve_times_s\": [";
       for (size_t i = 0; i < times.size(); ++i) j << (i ? ", " : "") << jnum(times[i]);
       j << "], \"steps\": [";
@@ -523,6 +539,8 @@ int main(int argc, char** argv) {
       group = std::make_unique<ShmGroup>(a.prob, parse_dims(a.decomp, lworld, a.prob.N), lworld, job_segment_name(),
                                          cpu_rank);
     }
+    W3D_REQUIRE(a.sources.empty() || (!group && lworld <= 1),
+                "sources: one rank only (ranks of a multi-process world are not supported)");
     W3D_REQUIRE(a.receivers.empty() || (!group && lworld <= 1),
                 "--receivers / --traces: one rank only (gathering traces from several processes is not implemented)");
     const int rc = a.cpu ? (group ? run_cpu_rank(a, *group, cpu_rank) : run_cpu(a)) : run_gpu(a);

@@ -154,6 +154,27 @@ inline double energy_value(const Problem& p, double kin, double pot) {
 void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox& box,
                   const double* s, double ct, ErrAcc* acc);
 
+// Point sources u_tt = Δu + Σ_q w_q(t) δ(x − x_q), δ discretised as 1/(hx·hy·hz) at the node: the addend of sample w at
+// a source node is a = τ²·w / (hx·hy·hz), evaluated by this one expression on every backend. The first level gets ½·a⁰
+// (the first step is a half step), level m + 1 gets a^m.
+inline double source_addend(const Problem& p, double w) { return ((p.tau * p.tau) * w) / ((p.hx() * p.hy()) * p.hz()); }
+// Validates a source list (Q global nodes strictly inside the grid, w[K][Q] finite; refusals start with "sources:") and
+// returns the scaled addends a[K][Q].
+std::vector<double> source_addends(const Problem& p, const i64* ijk, int Q, const double* w);
+
+// Response of a ZERO field to one source over a pass of s = 1..5 steps n → n + s (the leapfrog update is linear, so a
+// forced pass = the unforced pass + this): from r^{n−1} = r^n = 0, step k = 1..s advances with d2sum_t / leapfrog in
+// cpu_leapfrog's argument order and then adds a[k − 1] at `node` (first_is_start: the pass is the start, s = 1, and the
+// addend is ½·a[0]). out_last = r^{n+s}, out_prev = r^{n+s−1} on the kSourceSide³ cube around the node, C order, cell
+// (i, j, k) = node + (i, j, k) − kSourceRadius; non-zero only within L1 distance s − 1 / s − 2 of the node, and nodes on
+// or outside the global boundary stay +0.0. The bit-exact oracle of k_source_cone.
+constexpr int kSourceMaxSteps = 5;
+constexpr int kSourceRadius = kSourceMaxSteps;
+constexpr int kSourceSide = 2 * kSourceRadius + 1;
+constexpr int kSourceCells = kSourceSide * kSourceSide * kSourceSide;
+void cpu_source_response(const Problem& p, const Coeffs& c, const i64 node[3], const double* a, bool first_is_start, int s,
+                         double* out_last, double* out_prev);
+
 // Error of a stored field vs φ·ct over `box` (used for step 1 and for the standalone error check).
 void cpu_error(const Layout& l, const double* u, const LBox& box, const double* s, double ct, ErrAcc* acc);
 
@@ -201,6 +222,13 @@ class CpuSolver {
   void set_receivers(const i64* ijk, int R);
   const std::vector<double>& traces() const { return traces_; }
   int receivers() const { return static_cast<int>(recv_off_.size()); }
+  // Point sources: Q global nodes strictly inside the grid (ijk: Q triples; a node listed twice is added twice) and the
+  // wavelet samples w[K][Q], row m = w_q(m·τ). Every following run() adds, in list order, ½·a_q⁰ to u¹[x_q] after the
+  // start levels are stored, and a_q^m to u^{m+1}[x_q] after the plain leapfrog step m → m + 1 (m ≥ 1), with a =
+  // source_addend(w) — the plain definition, the oracle of the GPU source kernel. The error columns of the log then have
+  // no meaning (the eigenmode is no longer the solution). Q = 0 removes the sources. Not together with set_state.
+  void set_sources(const i64* ijk, int Q, const double* w);
+  int sources() const { return static_cast<int>(src_off_.size()); }
   // E^{K−1/2} of the last run()'s u^{K−1}, u^K (which = 0), or E^{1/2} of its u⁰, u¹ (which = 1; after set_initial)
   double energy(int which) const;
   // the sums behind energy(which): kin, pot, abs (the error scale) and the summation depth
@@ -208,6 +236,7 @@ class CpuSolver {
   // u^K (which = 0) or u^{K-1} (which = 1), padded local layout (single rank = whole domain).
   const std::vector<double>& field(int which) const { return which == 0 ? u_[final_] : u_[1 - final_]; }
   const Layout& layout() const { return lay_; }
+  const Problem& problem() const { return prob_; }
   std::vector<int> check_steps() const;
 
  private:
@@ -225,6 +254,8 @@ class CpuSolver {
   EnergySums e_start_;                   // of u⁰, u¹ of the last run() after set_initial
   std::vector<i64> recv_off_;            // receivers: Layout::off of each node
   std::vector<double> traces_;           // [K + 1][R] of the last run()
+  std::vector<i64> src_off_;             // sources: Layout::off of each node ...
+  std::vector<double> src_a_;            // ... and the scaled addends a[K][Q]
   int runs_ = 0;
 };
 

@@ -69,6 +69,21 @@ void launch_record_cone(const Layout& l, const Coeffs& c, const double* prev, co
 void launch_record_gather(const double* field, int n, const Receiver* table, int count, double* trace, i64 rtotal,
                           hipStream_t stream);
 
+// Point sources (kernels_source.hip; schedule.hpp Source / plan_sources; the oracle: cpu.hpp cpu_source_response).
+// Adds the response of a zero field to the forcing of a pass n → n + steps (steps = 1..5) to the pass's stored outputs:
+// out_last (u^{n+steps}) on the L1 ball of radius steps − 1 around every source of `table`, out_prev (u^{n+steps−1}) on
+// radius steps − 2 — on the nodes inside the global interior and inside the allocation of layout l (ghost layers
+// included; the source node itself may lie outside it), nothing else is addressed. `a`: device array [K][Q] of scaled
+// addends (cpu.hpp source_addend), column = Source::slot; step k adds a[n + k − 1]. start: the start level (n = 0,
+// steps = 1): out_last = u¹ gets ½·a[0]. One launch per colour class, in class order: class c = table[class_begin[c] ..
+// class_begin[c + 1]) (class_begin: host array of classes + 1 entries); the balls of a class are disjoint, so the
+// adds are plain loads and stores. With rcount > 0 (not for the start) level n + k's response at every receiver of
+// `rtable` within distance k − 1 of a source is added to trace[n + k][slot], k = 1..steps. Needs ghosts `steps` deep on
+// every axis the rank does not span; a null out_prev is refused.
+void launch_source_cone(const Layout& l, const Coeffs& c, double* out_prev, double* out_last, int n, int steps, bool start,
+                        const Source* table, const int* class_begin, int classes, const double* a, i64 Q,
+                        const Receiver* rtable, int rcount, double* trace, i64 rtotal, hipStream_t stream);
+
 // Runs one leapfrog step over up to 6 boxes in a single launch. If `partials` is non-null the error vs φ·ct is reduced
 // per workgroup into partials[0 .. leapfrog_blocks()).
 void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox* boxes, int nbox,

@@ -77,6 +77,10 @@ void load_initial(const std::string& prefix, const Problem& p, std::vector<doubl
 std::vector<i64> load_receivers(const std::string& path);
 void write_traces(const std::string& out, const Problem& p, const std::vector<i64>& ijk,
                   const std::vector<double>& values);
+// Point sources (--sources FILE): text, one "i j k f0 t0 amp" per line (blank lines and lines starting with # are
+// skipped): a global node and a Ricker wavelet w(t) = amp·(1 − 2π²f0²(t − t0)²)·exp(−π²f0²(t − t0)²). Fills the 3·Q
+// indices and the samples w[K][Q], row m = w_q(m·τ) (CpuSolver / GpuSolver / GpuGroup::set_sources); returns Q.
+int load_sources(const std::string& path, const Problem& p, std::vector<i64>& ijk, std::vector<double>& w);
 // PREFIX.prev / PREFIX.cur → u^{n0−1}, u^{n0}; returns n0
 int load_checkpoint(const std::string& prefix, const Problem& p, std::vector<double>& prev, std::vector<double>& cur);
 

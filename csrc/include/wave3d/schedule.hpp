@@ -173,7 +173,9 @@ struct UnitPlan {
 };
 
 // The units of a solve that starts at level start_n (1, 2 or a resumed step); analytic: the first is an analytic start.
-std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic);
+// sources: point sources are set (plan_sources) — the last unit then keeps both levels (no drop_prev: the correction is
+// added to the stored u^K after the pass, and rebuilding u^{K−1} would run the pass over it again).
+std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources = false);
 
 // --poison-ghosts where the messages land in the field buffers themselves (every schedule but the 3-D block passes,
 // whose receive regions k_box_copy fills): what a unit's exchange NaN-fills. `rows` runs of `count` doubles, `pitch`
@@ -225,6 +227,31 @@ struct Receiver {
 };
 std::vector<Receiver> plan_receivers(const Problem& p, const Dims& d, int rank, const Layout& l,
                                      const std::vector<std::array<i64, 3>>& nodes);
+
+// Point sources: grid nodes strictly inside the domain at which a forcing term is added after every step. Because the
+// leapfrog update is linear, a pass of s steps with forcing = the pass without + the response of a zero field to the
+// forcing, which is non-zero only on the L1 ball of radius s − 1 around the node (k_source_cone adds it to the pass's
+// two stored levels). plan_sources returns, for one rank, every source of the list whose L1 ball of `radius` meets the
+// rank's ALLOCATION (owned box plus ghost layers): a neighbour's source reaches into this rank's ghost planes, which
+// this rank corrects itself, so the node may lie outside the allocation (x, y, z and off are signed; off follows
+// Layout::off's formula and addresses memory only for nodes inside the allocation). Refused: a node on a global face or
+// outside the grid. The table is ordered by COLOUR CLASS, then by list order: classes are a greedy partition of the whole
+// list in list order in which two sources share a class only if their L1 distance exceeds 2·radius — their balls are
+// disjoint, so one launch per class adds without atomics; every rank computes the same classes, hence adds in the
+// same order. class_begin has one entry per class plus the end: class c = table[class_begin[c] .. class_begin[c + 1])
+// (possibly empty on this rank).
+struct Source {
+  i64 slot;     // index in the global list (the column of the addend array a[K][Q])
+  i64 x, y, z;  // local node, signed
+  i64 off;      // Layout::off's formula at (x, y, z)
+};
+struct SourcePlan {
+  std::vector<Source> table;
+  std::vector<int> class_begin;
+  int classes() const { return static_cast<int>(class_begin.size()) - 1; }
+};
+SourcePlan plan_sources(const Problem& p, const Dims& d, int rank, const Layout& l,
+                        const std::vector<std::array<i64, 3>>& nodes, int radius);
 
 // The global error log from the ranks' logs. Rank q's entry of step n is the pair xy[(q·(K+1) + n)·2 + {0, 1}] = (max
 // |e|, Σe²) over its nodes; per step of `checked`, in fixed rank order: the maximum (a NaN sticks) and Σe² summed left

@@ -133,6 +133,29 @@ class GpuSolver {
     std::vector<i64> slots;
   };
   Traces traces() const;
+  // Point sources: u_tt = Δu + Σ_q w_q(t) δ(x − x_q) at Q global nodes strictly inside the grid (ijk: Q triples; a node
+  // listed twice is added twice), w[K][Q] the wavelet samples, row m = w_q(m·τ) (cpu.hpp CpuSolver::set_sources: the
+  // definition). The pass kernels are untouched: by linearity a forced pass = the pass + the response of a zero field to
+  // its forcing, which k_source_cone (kernels_source.hip) adds to the pass's two stored levels — on s0, for the start
+  // right after the start levels are stored (before rows 0 and 1 of the traces are gathered), for unit i at the top of
+  // unit_shell(i + 1) (after the last unit: at the end of the solve), the point where the unit's exchange has been joined
+  // into s0.
+  //   Ghost invariant: exchanged ghost planes always carry UNCORRECTED values — every exchange of unit i's outputs
+  //   is complete before the correction of unit i — and every rank then corrects every node of its own allocation that
+  //   lies in a source's ball, ghost layers and the ghost_store plane included (plan_sources keeps the sources of the
+  //   neighbours whose balls reach in). The addend depends on the source, a and Coeffs only and the colour classes are
+  //   computed from the whole list, so a ghost node and its owner's node receive the same addends in the same order
+  //   and stay bit-equal. In a GpuGroup, lb_fence(i) puts every rank's s0 behind EVERY rank's pull of unit i (all_pulled),
+  //   so no rank corrects a region a peer has yet to read. (A single-step rank without overlap exchanges u^n before
+  //   unit n instead: there the owner's corrected value travels, and overwrites the ghost's own correction.)
+  // With sources the start stores u⁰, u¹ (no analytic start, no init2) and the last pass keeps both levels (no
+  // drop_prev: rebuilding u^{K−1} would run the pass over the corrected u^K). Nothing on the host per solve: the solve
+  // stays graph-captured and run_batch pipelined. The error log then has no meaning. Q = 0 removes the sources. Drops
+  // the captured graph. Refused (messages start with "sources:"): the push transport, fake_comm ranks, the two-step
+  // deep-halo schedule, the copy-engine transport (peers write this rank's ghosts on their own streams: the invariant
+  // is not argued for it), ranks of a multi-process world, and set_state together with sources.
+  void set_sources(const i64* ijk, int Q, const double* w);
+  int sources() const { return n_src_; }
   // Discrete energy (cpu.hpp cpu_energy): which = 0: E^{K−1/2} of the retained u^{K−1}, u^K; which = 1: E^{1/2},
   // computed inside the solve right after the first-step kernel (solves started by set_initial) and kept on the
   // device. One rank only. energy_sums: the kinetic and potential sums themselves.
@@ -299,6 +322,14 @@ class GpuSolver {
   int n_recv() const { return static_cast<int>(recv_.size()); }
   void record_stored(int n, const double* buf);  // row n from a stored level, on s0
   void record_unit(const UnitPlan& u);           // top of unit_shell: a fused unit's levels from its inputs, on s0
+  int n_src_ = 0;                     // set_sources: sources in the global list (on every rank, whatever it keeps)
+  SourcePlan src_;                    // the ones whose ball meets this rank's allocation, by colour class
+  Source* src_dev_ = nullptr;         // ... in device memory
+  double* src_a_ = nullptr;           // device: the scaled addends a[K][n_src_]
+  // the correction of the start level (u == nullptr: u¹ in `last`) or of unit u's outputs prev = u^{n+s−1}, last =
+  // u^{n+s}, on s0
+  void source_correct(const UnitPlan* u, double* prev, double* last);
+  void source_finish();  // end of the solve: the last unit's correction
   mutable Partial* energy_part_ = nullptr;  // k_energy's partials, then [n] = E^{K−1/2}'s sums, [n + 1] = E^{1/2}'s
   void energy_alloc() const;
   void drop_graphs();
@@ -444,6 +475,9 @@ class GpuGroup {
   // ranks' columns
   void set_receivers(const i64* ijk, int R);
   std::vector<double> traces() const;
+  // every rank (GpuSolver::set_sources: the loopback and rccl-self groups)
+  void set_sources(const i64* ijk, int Q, const double* w);
+  int sources() const { return ranks_[0]->sources(); }
 
  private:
   void enqueue();

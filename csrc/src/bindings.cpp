@@ -53,6 +53,17 @@ std::vector<std::array<i64, 3>> receiver_nodes(const iarr& a) {
   return v;
 }
 
+// sources: an (Q, 3) integer array of global node indices and the (K, Q) wavelet samples
+const double* source_w(const Problem& p, const iarr& nodes, const darr& w, int* Q) {
+  W3D_REQUIRE(nodes.size() == 0 || (nodes.ndim() == 2 && nodes.shape(1) == 3),
+              "sources: an (Q, 3) integer array of node indices");
+  *Q = nodes.size() == 0 ? 0 : static_cast<int>(nodes.shape(0));
+  W3D_REQUIRE(*Q == 0 || (w.ndim() == 2 && w.shape(0) == p.K && w.shape(1) == *Q),
+              "sources: w must have shape (K, Q) = (" + std::to_string(p.K) + ", " + std::to_string(*Q) +
+                  "): row m = the sources' samples at t = m tau");
+  return w.data();
+}
+
 template <class T>
 T* dptr(std::uintptr_t p) {
   return reinterpret_cast<T*>(p);
@@ -294,6 +305,27 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("problem"), py::arg("dims"), py::arg("rank"), py::arg("layout"), py::arg("nodes"),
         "this rank's receivers of the (R, 3) global node list: int64 rows (slot, x, y, z, off)");
+  m.def("plan_sources",
+        [](const Problem& p, const Dims& d, int rank, const Layout& l, const iarr& nodes, int radius) {
+          const SourcePlan v = plan_sources(p, d, rank, l, receiver_nodes(nodes), radius);
+          static_assert(sizeof(Source) == 5 * sizeof(i64), "a Source is five int64s");
+          iarr out({static_cast<py::ssize_t>(v.table.size()), static_cast<py::ssize_t>(5)});
+          if (!v.table.empty()) std::memcpy(out.mutable_data(), v.table.data(), v.table.size() * sizeof(Source));
+          return py::make_tuple(out, v.class_begin);
+        },
+        py::arg("problem"), py::arg("dims"), py::arg("rank"), py::arg("layout"), py::arg("nodes"), py::arg("radius"),
+        "the sources of the (Q, 3) global node list whose L1 ball of `radius` meets this rank's allocation, ordered by "
+        "colour class: (int64 rows (slot, x, y, z, off), class_begin)");
+  m.def("source_addend", &source_addend, py::arg("problem"), py::arg("w"), "tau^2 w / (hx hy hz)");
+  m.def("cpu_source_response",
+        [](const Problem& p, const Coeffs& c, const std::array<i64, 3>& node, const darr& a, bool start, int s) {
+          W3D_REQUIRE(a.size() >= (start ? 1 : s), "source_response: a holds fewer than s addends");
+          darr last({kSourceSide, kSourceSide, kSourceSide}), prev({kSourceSide, kSourceSide, kSourceSide});
+          cpu_source_response(p, c, node.data(), a.data(), start, s, last.mutable_data(), prev.mutable_data());
+          return py::make_tuple(last, prev);
+        },
+        py::arg("problem"), py::arg("coeffs"), py::arg("node"), py::arg("a"), py::arg("first_is_start"), py::arg("s"),
+        "(r^{n+s}, r^{n+s-1}) on the 11^3 cube around the node: the response of a zero field to the addends a[0..s)");
   m.def(
       "shell_split",
       [](const LBox& full, const std::vector<std::vector<bool>>& nbv) {
@@ -453,6 +485,12 @@ PYBIND11_MODULE(_C, m) {
         return darr({static_cast<py::ssize_t>(s.traces().size() / static_cast<size_t>(R)), static_cast<py::ssize_t>(R)},
                     s.traces().data());
       }, "the last run()'s (K+1, R) values, row n = u^n")
+      .def("set_sources", [](CpuSolver& s, const iarr& nodes, const darr& w) {
+        int Q = 0;
+        const double* wp = source_w(s.problem(), nodes, w, &Q);
+        s.set_sources(nodes.data(), Q, wp);
+      }, py::arg("nodes"), py::arg("w"), "point sources at these (Q, 3) global nodes with the (K, Q) samples w")
+      .def_property_readonly("sources", &CpuSolver::sources)
       .def("energy", &CpuSolver::energy, py::arg("which") = 0);
 
   // ---------------- GPU ----------------
@@ -526,6 +564,21 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("field"), py::arg("n"), py::arg("table"), py::arg("count"), py::arg("trace"), py::arg("rtotal"),
         py::arg("stream"), "k_record_gather: row n of trace from a stored level");
+  // sources: the table is plan_sources' array in device memory (a Source is its five int64s)
+  m.def("gpu_source_cone",
+        [](const Layout& l, const Coeffs& c, std::uintptr_t out_prev, std::uintptr_t out_last, int n, int steps, bool start,
+           std::uintptr_t table, const std::vector<int>& class_begin, std::uintptr_t a, i64 Q, std::uintptr_t rtable,
+           int rcount, std::uintptr_t trace, i64 rtotal, std::uintptr_t stream) {
+          W3D_REQUIRE(!class_begin.empty(), "source_cone: class_begin holds classes + 1 entries");
+          launch_source_cone(l, c, dptr<double>(out_prev), dptr<double>(out_last), n, steps, start,
+                             dptr<const Source>(table), class_begin.data(), static_cast<int>(class_begin.size()) - 1,
+                             dptr<const double>(a), Q, dptr<const Receiver>(rtable), rcount, dptr<double>(trace), rtotal,
+                             sptr(stream));
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("out_prev"), py::arg("out_last"), py::arg("n"), py::arg("steps"),
+        py::arg("start"), py::arg("table"), py::arg("class_begin"), py::arg("a"), py::arg("Q"), py::arg("rtable"),
+        py::arg("rcount"), py::arg("trace"), py::arg("rtotal"), py::arg("stream"),
+        "k_source_cone: adds the response to the forcing of a pass n -> n + steps to its outputs (and trace rows)");
   m.def("gpu_energy_depth", &energy_depth, "depth D of k_energy's reduction tree for this layout");
   m.def("gpu_energy_partials", &energy_partials);
   m.def("gpu_energy",
@@ -841,6 +894,12 @@ PYBIND11_MODULE(_C, m) {
         return py::make_tuple(v, t.slots);
       }, "the last solve's ((K+1, owned) values, the owned receivers' slots in the list)")
       .def_property_readonly("analytic_start", &GpuSolver::analytic_start)
+      .def("set_sources", [](GpuSolver& s, const iarr& nodes, const darr& w) {
+        int Q = 0;
+        const double* wp = source_w(s.problem(), nodes, w, &Q);
+        s.set_sources(nodes.data(), Q, wp);
+      }, py::arg("nodes"), py::arg("w"), "point sources at these (Q, 3) global nodes with the (K, Q) samples w")
+      .def_property_readonly("sources", &GpuSolver::sources)
       .def("energy", &GpuSolver::energy, py::arg("which") = 0,
            "discrete energy E^{K-1/2} (which = 0) / E^{1/2} (which = 1, after set_initial); one rank only")
       .def("energy_sums", [](const GpuSolver& s, int which) {
@@ -946,6 +1005,12 @@ PYBIND11_MODULE(_C, m) {
         const py::ssize_t rows = static_cast<py::ssize_t>(g.problem().K + 1);
         return darr({rows, static_cast<py::ssize_t>(t.size()) / rows}, t.data());
       }, "the last run()'s global (K+1, R) values, assembled from the ranks")
+      .def("set_sources", [](GpuGroup& g, const iarr& nodes, const darr& w) {
+        int Q = 0;
+        const double* wp = source_w(g.problem(), nodes, w, &Q);
+        g.set_sources(nodes.data(), Q, wp);
+      }, py::arg("nodes"), py::arg("w"))
+      .def_property_readonly("sources", &GpuGroup::sources)
       .def_property_readonly("transport", &GpuGroup::transport)
       .def_property_readonly("graph_enabled", &GpuGroup::graph_enabled)
       .def_property_readonly("world", &GpuGroup::world);

@@ -191,6 +191,61 @@ void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* o
   }
 }
 
+namespace {
+
+template <bool BOX>
+void source_response_impl(const Problem& p, const Coeffs& c, const i64 node[3], const double* a, bool start, int s,
+                          double* lv0, double* lv1) {
+  constexpr int S = kSourceSide, R = kSourceRadius;
+  auto cell = [](int i, int j, int k) { return ((i + R) * S + (j + R)) * S + (k + R); };
+  auto interior = [&](int i, int j, int k) {
+    return node[0] + i > 0 && node[0] + i < p.N && node[1] + j > 0 && node[1] + j < p.N && node[2] + k > 0 &&
+           node[2] + k < p.N;
+  };
+  double* lv[2] = {lv0, lv1};
+  int io = 0, ic = 1;  // level k is written over level k − 2
+  for (int k = 1; k <= s; ++k) {
+    const double* cu = lv[ic];
+    double* out = lv[io];
+    const int r = k - 1;
+    for (int i = -r; i <= r; ++i)
+      for (int j = -r; j <= r; ++j)
+        for (int m = -r; m <= r; ++m) {
+          if (std::abs(i) + std::abs(j) + std::abs(m) > r || !interior(i, j, m)) continue;
+          const int q = cell(i, j, m);
+          const double u = cu[q];
+          const double lap = d2sum_t<BOX>(u, cu[q - S * S], cu[q + S * S], cu[q - S], cu[q + S], cu[q - 1], cu[q + 1], c.ry, c.rz);
+          out[q] = leapfrog(u, out[q], lap, c.lam);
+        }
+    out[cell(0, 0, 0)] += start ? 0.5 * a[0] : a[k - 1];
+    const int t = io;
+    io = ic;
+    ic = t;
+  }
+  // lv[ic] = r^{n+s}, lv[io] = r^{n+s−1}: s odd leaves the last level in lv0
+  if (ic != 0)
+    for (int q = 0; q < kSourceCells; ++q) {
+      const double t = lv0[q];
+      lv0[q] = lv1[q];
+      lv1[q] = t;
+    }
+}
+
+}  // namespace
+
+void cpu_source_response(const Problem& p, const Coeffs& c, const i64 node[3], const double* a, bool first_is_start, int s,
+                         double* out_last, double* out_prev) {
+  W3D_REQUIRE(s >= 1 && s <= kSourceMaxSteps, "source_response: 1..5 steps");
+  W3D_REQUIRE(!first_is_start || s == 1, "source_response: the start is one step");
+  W3D_REQUIRE(node[0] > 0 && node[0] < p.N && node[1] > 0 && node[1] < p.N && node[2] > 0 && node[2] < p.N,
+              "source_response: the node is not strictly inside the grid");
+  for (int q = 0; q < kSourceCells; ++q) out_last[q] = out_prev[q] = 0.0;
+  if (c.box)
+    source_response_impl<true>(p, c, node, a, first_is_start, s, out_last, out_prev);
+  else
+    source_response_impl<false>(p, c, node, a, first_is_start, s, out_last, out_prev);
+}
+
 void cpu_error(const Layout& l, const double* u, const LBox& b, const double* s, double ct, ErrAcc* acc) {
   if (b.empty()) return;
   const i64 nxp = b.x1 - b.x0;

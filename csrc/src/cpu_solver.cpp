@@ -96,6 +96,8 @@ double CpuSolver::energy(int which) const {
 
 void CpuSolver::set_state(const double* prev, const double* cur, int n0) {
   W3D_REQUIRE(n0 >= 1 && n0 < prob_.K, "resume step must be in [1, K)");
+  W3D_REQUIRE(src_off_.empty(), "sources: not together with set_state (a resumed solve has no step 0 to start the "
+                                "wavelet from)");
   initial_ = false;
   init_[0].clear();
   init_[1].clear();
@@ -118,6 +120,34 @@ void CpuSolver::set_receivers(const i64* ijk, int R) {
   }
   recv_off_ = std::move(off);
   traces_.clear();
+}
+
+std::vector<double> source_addends(const Problem& p, const i64* ijk, int Q, const double* w) {
+  W3D_REQUIRE(Q >= 0 && (Q == 0 || (ijk != nullptr && w != nullptr)), "sources: bad source list");
+  for (int q = 0; q < Q; ++q) {
+    const i64 i = ijk[3 * q], j = ijk[3 * q + 1], k = ijk[3 * q + 2];
+    W3D_REQUIRE(i > 0 && i < p.N && j > 0 && j < p.N && k > 0 && k < p.N,
+                "sources: source " + std::to_string(q) + " = (" + std::to_string(i) + ", " + std::to_string(j) + ", " +
+                    std::to_string(k) + ") is not strictly inside the grid 1.." + std::to_string(p.N - 1) +
+                    " (a node on a global face or outside the grid)");
+  }
+  std::vector<double> a(static_cast<size_t>(p.K) * static_cast<size_t>(Q));
+  for (size_t m = 0; m < a.size(); ++m) {
+    W3D_REQUIRE(std::isfinite(w[m]), "sources: w[" + std::to_string(m / static_cast<size_t>(Q)) + "][" +
+                                         std::to_string(m % static_cast<size_t>(Q)) + "] is not finite");
+    a[m] = source_addend(p, w[m]);
+    W3D_REQUIRE(std::isfinite(a[m]), "sources: the scaled sample tau^2 w / (hx hy hz) overflows");
+  }
+  return a;
+}
+
+void CpuSolver::set_sources(const i64* ijk, int Q, const double* w) {
+  W3D_REQUIRE(Q == 0 || resume_n_ == 0, "sources: not together with set_state (a resumed solve has no step 0 to start "
+                                        "the wavelet from)");
+  std::vector<double> a = source_addends(prob_, ijk, Q, w);
+  src_off_.clear();
+  for (int q = 0; q < Q; ++q) src_off_.push_back(lay_.off(ijk[3 * q], ijk[3 * q + 1], ijk[3 * q + 2]));
+  src_a_ = std::move(a);
 }
 
 std::vector<int> CpuSolver::check_steps() const {
@@ -154,6 +184,13 @@ CpuResult CpuSolver::run() {
   } else {
     cpu_init_first(lay_, c, s, u_[0].data(), u_[1].data());
   }
+  // sources: level m + 1 gets a^m at every source node, in list order (the start level u¹: ½·a⁰)
+  const size_t nsrc = src_off_.size();
+  auto add_sources = [&](int m, double scale, std::vector<double>& u) {
+    for (size_t q = 0; q < nsrc; ++q)
+      u[static_cast<size_t>(src_off_[q])] += scale * src_a_[static_cast<size_t>(m) * nsrc + q];
+  };
+  if (nsrc > 0) add_sources(0, 0.5, u_[1]);
   const size_t nrec = recv_off_.size();
   auto trace_row = [&](int n, const std::vector<double>& u) {
     for (size_t k = 0; k < nrec; ++k) traces_[static_cast<size_t>(n) * nrec + k] = u[static_cast<size_t>(recv_off_[k])];
@@ -182,6 +219,7 @@ CpuResult CpuSolver::run() {
     }
     r.compute_s += now_s() - tc;
     std::swap(cur, old);
+    if (nsrc > 0) add_sources(n, 1.0, u_[cur]);
     if (nrec > 0) trace_row(n + 1, u_[cur]);
   }
   final_ = cur;

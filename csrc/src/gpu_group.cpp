@@ -142,6 +142,18 @@ void GpuGroup::set_receivers(const i64* ijk, int R) {
   exec_ = nullptr;  // (graph_ stays as it is: the record launches are device work like any other)
 }
 
+void GpuGroup::set_sources(const i64* ijk, int Q, const double* w) {
+  W3D_REQUIRE(Q == 0 || !multi_, "sources: not on a multi-device group (its ranks solve on their own threads over RCCL; "
+                                 "use a loopback or rccl-self group)");
+  for (auto& r : ranks_) {
+    DeviceScope scope(r->device());
+    r->set_sources(ijk, Q, w);
+  }
+  if (multi_) return;
+  if (exec_) W3D_HIP(hipGraphExecDestroy(exec_));
+  exec_ = nullptr;  // (graph_ stays as it is: the corrections are device work like any other)
+}
+
 std::vector<double> GpuGroup::traces() const {
   W3D_REQUIRE(n_recv_ > 0, "traces: no receivers are set (set_receivers)");
   const size_t rows = static_cast<size_t>(ranks_[0]->sch_.prob.K + 1), R = static_cast<size_t>(n_recv_);
@@ -236,6 +248,7 @@ void GpuGroup::enqueue() {
       for (auto* s : rs) s->unit_interior(i);
     step("interior", i);
   }
+  for (auto* s : rs) s->source_finish();
   for (auto* s : rs) s->flush_reduces();
   for (auto* s : rs)
     if (s->sch_.push) {

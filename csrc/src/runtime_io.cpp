@@ -161,6 +161,35 @@ void write_traces(const std::string& out, const Problem& p, const std::vector<i6
   j << "]}\n";
 }
 
+int load_sources(const std::string& path, const Problem& p, std::vector<i64>& ijk, std::vector<double>& w) {
+  std::ifstream f(path);
+  W3D_REQUIRE(static_cast<bool>(f), "sources: cannot read " + path);
+  ijk.clear();
+  std::vector<double> par;  // f0, t0, amp per source
+  std::string line;
+  for (int no = 1; std::getline(f, line); ++no) {
+    const size_t b = line.find_first_not_of(" \t\r");
+    if (b == std::string::npos || line[b] == '#') continue;
+    long long i = 0, j = 0, k = 0;
+    double f0 = 0.0, t0 = 0.0, amp = 0.0;
+    char extra = 0;
+    W3D_REQUIRE(std::sscanf(line.c_str(), "%lld %lld %lld %lf %lf %lf %c", &i, &j, &k, &f0, &t0, &amp, &extra) == 6,
+                "sources: " + path + " line " + std::to_string(no) + ": expected i j k f0 t0 amp");
+    ijk.insert(ijk.end(), {static_cast<i64>(i), static_cast<i64>(j), static_cast<i64>(k)});
+    par.insert(par.end(), {f0, t0, amp});
+  }
+  W3D_REQUIRE(!ijk.empty(), "sources: " + path + " lists no source");
+  const size_t Q = ijk.size() / 3;
+  w.assign(static_cast<size_t>(p.K) * Q, 0.0);
+  for (int m = 0; m < p.K; ++m)
+    for (size_t q = 0; q < Q; ++q) {
+      const double t = static_cast<double>(m) * p.tau - par[3 * q + 1];
+      const double x = (M_PI * par[3 * q] * t) * (M_PI * par[3 * q] * t);
+      w[static_cast<size_t>(m) * Q + q] = (1.0 - 2.0 * x) * std::exp(-x) * par[3 * q + 2];
+    }
+  return static_cast<int>(Q);
+}
+
 // --resume PREFIX: u^{n0−1} from PREFIX.prev, u^{n0} from PREFIX.cur; returns n0
 int load_checkpoint(const std::string& prefix, const Problem& p, std::vector<double>& prev, std::vector<double>& cur) {
   const int sc = load_dump_global(prefix + ".cur", p, cur);

@@ -260,7 +260,7 @@ void plan_msgs(const RankSchedule& s, UnitPlan& u) {
 
 }  // namespace
 
-std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic) {
+std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources) {
   std::vector<UnitPlan> units;
   const int K = s.prob.K;
   int n = start_n;
@@ -297,7 +297,9 @@ std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analyt
   // nothing inside the solve reads the last pass's u^{K−1}: no pass follows, and no exchange sends it. (Not under
   // --poison-ghosts on the copy-engine transport: its end of solve NaN-fills the ghost regions of buffers 2 and 3 for
   // the next solve's first exchange, and those can be the last unit's inputs, which a rebuild reads again.)
-  if (nu > 0 && !s.opt.keep_prev && s.nbuf == 4 && !s.push && !(s.sdma && s.opt.poison_ghosts) &&
+  // (Nor with point sources: the source correction is added to the stored u^K after the pass, and a rebuild runs the
+  // pass again over it.)
+  if (nu > 0 && !sources && !s.opt.keep_prev && s.nbuf == 4 && !s.push && !(s.sdma && s.opt.poison_ghosts) &&
       ((s.mode == Mode::kFusedSingle && s.opt.tb) || tb)) {
     UnitPlan& u = units.back();
     u.drop_prev = u.fused() && !u.exchange && runs_p2(s, u.steps, u.analytic);
@@ -399,6 +401,62 @@ std::vector<Receiver> plan_receivers(const Problem& p, const Dims& d, int rank, 
     v.push_back(Receiver{static_cast<i64>(r), x, y, z, l.off(x, y, z)});
   }
   return v;
+}
+
+SourcePlan plan_sources(const Problem& p, const Dims& d, int rank, const Layout& l,
+                        const std::vector<std::array<i64, 3>>& nodes, int radius) {
+  const Box b = rank_box(p, d, rank);
+  W3D_REQUIRE(l.gx0 == b.x0 && l.gy0 == b.y0 && l.gz0 == b.z0 && l.nx == b.nx() && l.ny == b.ny() && l.nz == b.nz(),
+              "plan_sources: the layout is not this rank's");
+  W3D_REQUIRE(radius >= 0, "plan_sources: negative radius");
+  const size_t Q = nodes.size();
+  for (size_t q = 0; q < Q; ++q) {
+    const i64 i = nodes[q][0], j = nodes[q][1], k = nodes[q][2];
+    W3D_REQUIRE(i > 0 && i < p.N && j > 0 && j < p.N && k > 0 && k < p.N,
+                "sources: source " + std::to_string(q) + " = (" + std::to_string(i) + ", " + std::to_string(j) + ", " +
+                    std::to_string(k) + ") is not strictly inside the grid 1.." + std::to_string(p.N - 1) +
+                    " (a node on a global face or outside the grid)");
+  }
+  // colour classes over the WHOLE list (every rank computes the same ones): greedy in list order, a source joins the
+  // first class whose members are all farther than 2·radius from it
+  std::vector<int> colour(Q, 0);
+  std::vector<std::vector<size_t>> classes;
+  auto dist = [&](size_t a, size_t c) {
+    i64 s = 0;
+    for (int k = 0; k < 3; ++k) s += nodes[a][k] > nodes[c][k] ? nodes[a][k] - nodes[c][k] : nodes[c][k] - nodes[a][k];
+    return s;
+  };
+  for (size_t q = 0; q < Q; ++q) {
+    size_t c = 0;
+    for (; c < classes.size(); ++c) {
+      bool ok = true;
+      for (size_t m : classes[c])
+        if (dist(q, m) <= 2 * static_cast<i64>(radius)) {
+          ok = false;
+          break;
+        }
+      if (ok) break;
+    }
+    if (c == classes.size()) classes.emplace_back();
+    classes[c].push_back(q);
+    colour[q] = static_cast<int>(c);
+  }
+  // this rank's: the L1 ball meets the allocation [−g, n + g) on every axis (the L1 distance from the node to the box)
+  SourcePlan out;
+  out.class_begin.push_back(0);
+  const i64 lo[3] = {-l.xg, -l.yg, -l.zg}, hi[3] = {l.nx + l.xg - 1, l.ny + l.yg - 1, l.nz + l.zg - 1};
+  for (const std::vector<size_t>& cl : classes) {
+    for (size_t q : cl) {
+      const i64 loc[3] = {nodes[q][0] - b.x0, nodes[q][1] - b.y0, nodes[q][2] - b.z0};
+      i64 away = 0;
+      for (int k = 0; k < 3; ++k) away += loc[k] < lo[k] ? lo[k] - loc[k] : loc[k] > hi[k] ? loc[k] - hi[k] : 0;
+      if (away > radius) continue;
+      // (off: Layout::off's formula on signed nodes; outside the allocation it addresses nothing and is never used alone)
+      out.table.push_back(Source{static_cast<i64>(q), loc[0], loc[1], loc[2], l.off(loc[0], loc[1], loc[2])});
+    }
+    out.class_begin.push_back(static_cast<int>(out.table.size()));
+  }
+  return out;
 }
 
 ErrorLog combine_error_log(const double* xy, int nsrc, int K, int N, const std::vector<int>& checked) {

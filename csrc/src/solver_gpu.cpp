@@ -175,6 +175,8 @@ GpuSolver::~GpuSolver() {
   if (energy_part_) (void)hipFree(energy_part_);
   if (recv_dev_) (void)hipFree(recv_dev_);
   if (trace_) (void)hipFree(trace_);
+  if (src_dev_) (void)hipFree(src_dev_);
+  if (src_a_) (void)hipFree(src_a_);
   if (partials_) (void)hipFree(partials_);
   if (tb_partials_) (void)hipFree(tb_partials_);
   if (errlog_) (void)hipFree(errlog_);
@@ -203,7 +205,8 @@ size_t GpuSolver::device_bytes() const {
          static_cast<size_t>(sch_.prob.N + 3) * sizeof(double) + tb_bytes_ +
          ((init_[0] ? 1u : 0u) + (init_[1] ? 1u : 0u)) * static_cast<size_t>(init_lay_.bytes()) +
          (energy_part_ ? static_cast<size_t>(energy_partials(sch_.lay) + 2) * sizeof(Partial) : 0u) +
-         recv_.size() * (sizeof(Receiver) + static_cast<size_t>(sch_.prob.K + 1) * sizeof(double));
+         recv_.size() * (sizeof(Receiver) + static_cast<size_t>(sch_.prob.K + 1) * sizeof(double)) +
+         src_.table.size() * sizeof(Source) + (src_a_ ? static_cast<size_t>(sch_.prob.K) * n_src_ * sizeof(double) : 0u);
 }
 
 void GpuSolver::drop_graphs() {
@@ -299,6 +302,49 @@ void GpuSolver::record_unit(const UnitPlan& u) {
   launch_record_cone(sch_.lay, coef_, u_[old_], u_[cur_], u.n, u.steps, recv_dev_, n_recv(), trace_, n_recv(), s0_);
 }
 
+void GpuSolver::set_sources(const i64* ijk, int Q, const double* w) {
+  if (Q > 0) {
+    W3D_REQUIRE(!sch_.push, "sources: not on the push transport (its ghost planes live in the staging buffers, which the "
+                            "source kernel does not correct); use a loopback or rccl-self group");
+    W3D_REQUIRE(!sch_.opt.fake_comm, "sources: a fake rank's ghosts are never delivered");
+    W3D_REQUIRE(sch_.mode != Mode::kDeep, "sources: the two-step deep-halo passes start from the analytic pair only; use "
+                                          "the LDS passes or temporal = 1");
+    W3D_REQUIRE(!sch_.sdma, "sources: not on the copy-engine transport (peers write this rank's ghost planes on their "
+                            "own streams; that they carry uncorrected values is not argued for it yet)");
+    W3D_REQUIRE(sch_.world == 1 || loopback_, "sources: one rank or an in-process group only (ranks of a multi-process "
+                                              "world are not supported)");
+    W3D_REQUIRE(resume_n_ == 0, "sources: not together with set_state (a resumed solve has no step 0 to start the "
+                                "wavelet from)");
+  }
+  const std::vector<double> a = source_addends(sch_.prob, ijk, Q, w);  // (refuses bad nodes and samples)
+  std::vector<std::array<i64, 3>> nodes(static_cast<size_t>(Q));
+  for (int q = 0; q < Q; ++q) nodes[static_cast<size_t>(q)] = {ijk[3 * q], ijk[3 * q + 1], ijk[3 * q + 2]};
+  // (radius: the largest ball any pass needs, so one plan and one set of colour classes serves every unit)
+  SourcePlan plan = plan_sources(sch_.prob, sch_.dims, sch_.rank, sch_.lay, nodes, kSourceMaxSteps - 1);
+  DeviceScope scope(dev_, true);
+  drop_graphs();
+  if (src_dev_) W3D_HIP(hipFree(src_dev_));
+  if (src_a_) W3D_HIP(hipFree(src_a_));
+  src_dev_ = nullptr;
+  src_a_ = nullptr;
+  src_ = std::move(plan);
+  n_src_ = Q;
+  if (src_.table.empty()) return;
+  W3D_HIP(hipMalloc(&src_dev_, src_.table.size() * sizeof(Source)));
+  W3D_HIP(hipMemcpy(src_dev_, src_.table.data(), src_.table.size() * sizeof(Source), hipMemcpyHostToDevice));
+  W3D_HIP(hipMalloc(&src_a_, a.size() * sizeof(double)));
+  W3D_HIP(hipMemcpy(src_a_, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice));
+}
+
+void GpuSolver::source_correct(const UnitPlan* u, double* prev, double* last) {
+  if (src_.table.empty()) return;
+  timed(kPhaseCompute, s0_, [&] {
+    launch_source_cone(sch_.lay, coef_, prev, last, u ? u->n : 0, u ? u->steps : 1, u == nullptr, src_dev_,
+                       src_.class_begin.data(), src_.classes(), src_a_, n_src_, u ? recv_dev_ : nullptr, u ? n_recv() : 0,
+                       trace_, n_recv(), s0_);
+  });
+}
+
 Partial GpuSolver::energy_sums(int which) const {
   W3D_REQUIRE(sch_.world == 1, "energy: one rank only (multi-rank: Solver.energy assembles the global fields)");
   W3D_REQUIRE(which == 0 || which == 1, "energy: which is 0 (E at K-1/2) or 1 (E at 1/2)");
@@ -326,6 +372,7 @@ void GpuSolver::set_state(const double* prev, const double* cur, int n0) {
   W3D_REQUIRE(n0 >= 1 && n0 < sch_.prob.K, "resume step must be in [1, K)");
   W3D_REQUIRE(sch_.mode != Mode::kDeepTb || sch_.prob.K - n0 >= 2, "resume: the multi-rank LDS passes need >= 2 steps left");
   W3D_REQUIRE(sch_.mode != Mode::kDeep || (sch_.prob.K - n0) % 2 == 0, "resume: two-step passes need an even step count left");
+  W3D_REQUIRE(n_src_ == 0, "sources: not together with set_state (a resumed solve has no step 0 to start the wavelet from)");
   if (initial_) {  // (the two starts replace each other)
     W3D_HIP(hipDeviceSynchronize());
     for (double*& p : init_) {
@@ -387,7 +434,8 @@ void GpuSolver::phase_init() {
     W3D_HIP(hipMemsetAsync(trace_, 0xFF, static_cast<size_t>(K + 1) * recv_.size() * sizeof(double), s0_));
   // one rank on the LDS kernel: the first pass starts from the analytic u⁰, u¹ itself (no init kernel, no reads)
   analytic_ = (sch_.mode == Mode::kFusedSingle || sch_.mode == Mode::kDeepTb) && sch_.analytic_ok() && resume_n_ == 0 &&
-              !initial_ && !recording_;  // (receivers: both start levels are stored, rows 0 and 1 are gathered)
+              !initial_ && !recording_ && n_src_ == 0;  // (receivers: both start levels are stored, rows 0 and 1 are
+                                                        // gathered; sources: u¹ is corrected in memory)
   if (resume_n_ > 0) {  // loaded state: u^{n0−1} → buf 0, u^{n0} → buf 1 (ghosts included)
     const size_t bytes = static_cast<size_t>(sch_.lay.bytes());
     timed(kPhaseInit, s0_, [&] {
@@ -410,7 +458,7 @@ void GpuSolver::phase_init() {
     start_n_ = 1;
   } else if (analytic_) {
     start_n_ = 1;
-  } else if (sch_.opt.init2 && K >= 2 && !recording_) {
+  } else if (sch_.opt.init2 && K >= 2 && !recording_ && n_src_ == 0) {
     // u¹ -> buf 0, u² -> buf 1 analytically (no read pass), ghosts included; the first leapfrog step is n = 2
     timed(kPhaseInit, s0_, [&] {
       launch_init_two(sch_.lay, coef_, s, u_[0], u_[1], ct_[2], is_check_[2] ? partials_ : nullptr, s0_);
@@ -425,6 +473,8 @@ void GpuSolver::phase_init() {
     timed(kPhaseCheck, s0_, [&] { check_stored(1, u_[1]); });
     start_n_ = 1;
   }
+  // sources: ½·a⁰ on u¹ (every start above but init2 left u⁰ in buffer 0 and u¹ in buffer 1), before the gathers below
+  if (n_src_ > 0) source_correct(nullptr, u_[0], u_[1]);
   if (recording_) {  // (every start above but init2 left u^{start−1} in buffer 0 and u^{start} in buffer 1)
     timed(kPhaseCheck, s0_, [&] {
       record_stored(start_n_ - 1, u_[0]);
@@ -433,7 +483,7 @@ void GpuSolver::phase_init() {
   }
   cur_ = 1;
   old_ = 0;
-  units_ = plan_units(sch_, start_n_, analytic_);
+  units_ = plan_units(sch_, start_n_, analytic_, n_src_ > 0);
   if (sch_.push) push_upload();
 }
 
@@ -454,6 +504,10 @@ void GpuSolver::unit_shell(int i) {
   }
   // (s0: every pass of the unit follows it there — the shells on the side stream wait for ev_shell_, recorded below —
   // and the previous unit's passes, which read that plane of the same buffer as a ghost, precede it)
+  // sources: the previous unit's outputs (old_, cur_ since its unit_interior) get its forcing's response before anything
+  // reads them. Its exchange has been joined into s0 (in a group: every rank's, lb_fence), so the ghost planes that
+  // travelled carried uncorrected values and every rank corrects its own allocation (solver.hpp set_sources).
+  if (n_src_ > 0 && i > 0) source_correct(&units_[static_cast<size_t>(i) - 1], u_[old_], u_[cur_]);
   if (sch_.opt.poison_ghosts && u.ghost_bits) poison(u, uf_, s0_, true);
   // receivers: the unit's levels from its inputs, whose ghosts are complete here (the previous unit's exchange has been
   // joined into s0) and which nothing writes before the next unit's pass
@@ -720,6 +774,11 @@ void GpuSolver::unit_interior(int i) {
   prev_buf_ = old_;
 }
 
+// sources: the last unit's correction, at the end of the solve (no unit_shell follows it)
+void GpuSolver::source_finish() {
+  if (n_src_ > 0 && !units_.empty()) source_correct(&units_.back(), u_[old_], u_[cur_]);
+}
+
 void GpuSolver::flush_reduces() {
   if (pending_.empty()) return;
   timed(kPhaseCheck, s0_, [&] { launch_reduce_batch(pending_.data(), static_cast<int>(pending_.size()), s0_); });
@@ -742,6 +801,7 @@ void GpuSolver::enqueue_solve() {
     unit_interior(i);
     if (late) unit_exchange(i);
   }
+  source_finish();
   flush_reduces();
   if (sch_.push) push_finish(s0_);
   if (sch_.sdma) sdma_finish();

@@ -58,6 +58,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="record u at grid nodes for every step 0..K: FILE lists one node per line as i j k")
     ap.add_argument("--traces", default="", metavar="OUT",
                     help="write the recorded (K+1) x R values to OUT.bin / OUT.json (utils/dump.py load_traces)")
+    ap.add_argument("--sources", default="", metavar="FILE",
+                    help="point sources w(t) delta(x - x_s): FILE lists one source per line as i j k f0 t0 amp (a node "
+                         "strictly inside the grid and a Ricker wavelet of peak frequency f0 centred at t0); the error "
+                         "lines then have no meaning (backends hip and cpu; not with --resume)")
     ap.add_argument("--force", action="store_true", help="run even if the CFL condition is violated")
     ap.add_argument("--quiet", action="store_true")
     return ap
@@ -83,6 +87,8 @@ def main(argv=None) -> int:
         ap.error("--initial and --resume exclude each other")
     if a.energy and not a.initial:
         ap.error("--energy needs --initial (E(1/2) is kept by solves that start from it)")
+    if a.sources and a.resume:
+        ap.error("--sources and --resume exclude each other")
     if bool(a.receivers) != bool(a.traces):
         ap.error("--receivers FILE and --traces OUT go together")
     import torch
@@ -158,6 +164,17 @@ def main(argv=None) -> int:
             return 2
         nodes = dumpio.load_receivers(a.receivers)
         s.set_receivers(nodes)
+    n_sources = 0
+    if a.sources:
+        if world > 1:
+            print("wave3d: sources: one rank (or --world P in this process) only; ranks of a multi-process world are not "
+                  "supported", file=sys.stderr)
+            return 2
+        from .utils.wavelets import load_sources
+
+        src_nodes, src_w = load_sources(a.sources, a.tau, a.K)
+        s.set_sources(src_nodes, src_w)
+        n_sources = int(src_nodes.shape[0])
     r = None
     times = []
     for i in range(a.warmup + a.repeat):
@@ -191,6 +208,7 @@ def main(argv=None) -> int:
                            **({"box": list(spec.edges)} if spec.is_box else {}), "ranks": s.world, "dims": list(s.dims), "solve_s": best,
                            "gcell_per_s": gcell_per_s(a.N, a.K, best),
                            **({"energy_start": e_start, "energy_end": e_end} if a.energy else {}),
+                           **({"sources": n_sources} if a.sources else {}),
                            "steps": [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]}, f)
     if a.traces:
         dumpio.save_traces(a.traces, s.traces().numpy(), nodes, N=a.N, K=a.K, L=a.L, tau=a.tau, box=spec.edges)

@@ -407,6 +407,56 @@ class Solver:
         self._impl.set_receivers(a)
         self._receivers = a.shape[0]
 
+    def set_sources(self, nodes, w) -> None:
+        """Point sources: solve u_tt = Δu + Σ_q w_q(t)·δ(x − x_q). ``nodes`` is a (Q, 3) integer array of GLOBAL node
+        indices strictly inside the grid (1..N−1; a node listed twice is added twice), ``w`` a (K, Q) float array, row m
+        = the sources' samples w_q(m·τ) (``utils.wavelets.ricker`` makes a column). The δ is 1/(hx·hy·hz) at the node;
+        the solver does the scaling: u¹[x_q] += ½·a⁰ after the start, u^{m+1}[x_q] += a^m after step m → m+1, a =
+        τ²·w/(hx·hy·hz). The HIP backend keeps its schedule — fused passes, hipGraph, run_batch, in-process loopback
+        and rccl-self groups: by linearity a forced pass is the pass plus the response of a zero field to its forcing,
+        which ``k_source_cone`` adds to the pass's stored levels — except that the start stores u⁰ and u¹ and the
+        last pass keeps u^{K−1}. With sources the error columns of the result have no meaning (the eigenmode is no
+        longer the solution), and ``energy()`` is no longer conserved. An empty list removes the sources. Combines
+        with ``set_initial`` and ``set_receivers``; not with ``set_state``, the push or copy-engine transports, or
+        several processes."""
+        import numpy as np
+
+        if self.runtime == "process":
+            raise NotImplementedError("sources: runtime='process' is out of scope (the rank processes take no source "
+                                      "list); run in process, or use bin/wave3d --sources")
+        C = load()
+        native = isinstance(self._impl, (C.GpuGroup, C.CpuSolver)) or (isinstance(self._impl, C.GpuSolver)
+                                                                        and self.world == 1)
+        if not native:
+            raise NotImplementedError("sources: the native cpu backend, one hip rank, or an in-process hip group only "
+                                      "(ranks of a multi-process world are not supported)")
+        a = np.asarray(nodes.cpu().numpy() if isinstance(nodes, torch.Tensor) else nodes)
+        if a.size and (a.ndim != 2 or a.shape[1] != 3):
+            raise ValueError(f"sources: expected a (Q, 3) array of node indices, got shape {a.shape}")
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("sources: node indices are integers")
+        a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1, 3)
+        Q, N, K = a.shape[0], self.spec.N, self.spec.K
+        wv = np.ascontiguousarray(w.cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float64)
+        if Q == 0:
+            wv = np.zeros((K, 0))
+        if wv.shape != (K, Q):
+            raise ValueError(f"sources: w must have shape (K, Q) = ({K}, {Q}), got {wv.shape}")
+        if not np.isfinite(wv).all():
+            raise ValueError("sources: w holds non-finite values")
+        bad = np.nonzero(((a < 1) | (a > N - 1)).any(axis=1))[0]
+        if bad.size:
+            q = int(bad[0])
+            raise ValueError(f"sources: source {q} = {tuple(int(v) for v in a[q])} is not strictly inside the grid "
+                             f"1..{N - 1} (a node on a global face or outside the grid)")
+        self._impl.set_sources(a, wv)
+        self._sources = Q
+
+    @property
+    def sources(self) -> int:
+        """Number of point sources set by ``set_sources``."""
+        return getattr(self, "_sources", 0)
+
     def traces(self) -> torch.Tensor:
         """The last run()'s recorded values: a (K+1, R) float64 CPU tensor, row n = u^n at the R receivers in the order
         ``set_receivers`` got them (run_batch: its last solve's). Rows below step − 1 of a ``set_state`` start are NaN."""

@@ -51,6 +51,7 @@ LIB_SOURCES = [
     ("src/kernels_init2.hip", "hip"),
     ("src/kernels_initial.hip", "hip"),
     ("src/kernels_record.hip", "hip"),
+    ("src/kernels_source.hip", "hip"),
     ("src/kernels_leapfrog_tb.hip", "hip"),
     ("src/kernels_leapfrog_tb_push.hip", "hip"),
     ("src/kernels_leapfrog_p2.hip", "hip"),

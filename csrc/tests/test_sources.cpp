@@ -7,7 +7,8 @@
 //   * the split identity and its rounding: CpuSolver with sources against unforced cpu_leapfrog passes plus the
 //     responses (superposition), from seeded initial data. Prints d_split = max |difference| and umax = max |u| for
 //     every configuration: N = 24 with one source and a 5 + 5 split, and the N = 40, K = 12 cube and box configurations
-//     of tests/sources_common.py (5 + 5 + 1), whose figures set the tolerance of the fused GPU solves.
+//     of tests/sources_common.py (5 + 5 + 1), whose figures set the tolerance of the fused GPU solves; and the K = 203
+//     shot of tests/long_reference.py (two Ricker sources into a field at rest, 40 x 5 + 2), cube and box.
 //
 // Built and run by CMake/ctest (CMakeLists.txt) and, with host AddressSanitizer + UBSan, by
 // tests/test_sources_native.py. Exit status 0 = all checks passed; every failure prints its location.
@@ -224,9 +225,19 @@ void check_response(i64 N, const Node& node, bool box) {
   }
 }
 
+// the long shot's wavelets: Ricker samples rounded to multiples of 2^-16, the same formula as tests/long_reference.py
+// ricker16 (the rounding keeps the last bits of exp out of the samples; their sum is exact in any order)
+double ricker16(double f0, double t0, double tau, int m, double amp) {
+  const double t = static_cast<double>(m) * tau - t0;
+  const double a = (3.141592653589793 * f0) * t;
+  return std::nearbyint(amp * ((1.0 - 2.0 * (a * a)) * std::exp(-(a * a))) * 65536.0) / 65536.0;
+}
+
 // The split identity: CpuSolver with sources against passes of `split` steps without forcing plus the responses.
+// long_shot: zero initial data and the two Ricker wavelets of tests/long_reference.py long_shot instead of the seeded
+// data and the dyadic test wavelet.
 void check_split(const char* name, i64 N, int K, bool box, double tau, const std::vector<Node>& nodes,
-                 const std::vector<int>& split) {
+                 const std::vector<int>& split, bool long_shot = false) {
   Problem p = make(N, K, box);
   p.tau = tau;
   p.validate();
@@ -239,6 +250,16 @@ void check_split(const char* name, i64 N, int K, bool box, double tau, const std
   for (double& v : psi) v = g.next();
   for (int m = 0; m < K; ++m)
     for (int q = 0; q < Q; ++q) w[static_cast<size_t>(m) * Q + q] = wavelet(m, q);
+  if (long_shot) {
+    CHECK(Q == 2);
+    std::fill(phi.begin(), phi.end(), 0.0);
+    std::fill(psi.begin(), psi.end(), 0.0);
+    const double f0[2] = {static_cast<double>(N) / 10.0, static_cast<double>(N) / 8.0}, amp[2] = {1.0, -0.75};
+    double wsum = 0.0;
+    for (int m = 0; m < K; ++m)
+      for (int q = 0; q < 2; ++q) wsum += std::fabs(w[static_cast<size_t>(m) * 2 + q] = ricker16(f0[q], 1.5 / f0[q], tau, m, amp[q]));
+    std::printf("long-shot %s: tau = %.17g sum |w| = %.17g\n", name, tau, wsum);
+  }
   const std::vector<i64> ijk = flat(nodes);
   CpuSolver ref(p, 0, 0);
   ref.set_initial(phi.data(), psi.data());
@@ -270,6 +291,7 @@ void check_split(const char* name, i64 N, int K, bool box, double tau, const std
   for (int q = 0; q < Q; ++q) add(nodes[static_cast<size_t>(q)], q, 0, 1, true, u[1], u[0]);
   const std::vector<double> table = sin_table_ext(p);
   int cur = 1, old = 0, n = 1, total = 0;
+  double umax_run = 0.0;
   for (int s : split) total += s;
   CHECK(1 + total == K);
   for (int s : split) {
@@ -279,8 +301,13 @@ void check_split(const char* name, i64 N, int K, bool box, double tau, const std
     }
     for (int q = 0; q < Q; ++q) add(nodes[static_cast<size_t>(q)], q, n, s, false, u[cur], u[old]);
     n += s;
+    // (the long shot: its largest values occur while the wavelets fire, long before K, and the traces hold them — umax is
+    // taken over the levels at every pass boundary, not over the two last levels alone)
+    if (long_shot)
+      for (const std::vector<double>* f : {&u[cur], &u[old]})
+        for (double v : *f) umax_run = std::fmax(umax_run, std::fabs(v));
   }
-  double d_split = 0.0, umax = 0.0;
+  double d_split = 0.0, umax = umax_run;
   for (int which = 0; which < 2; ++which) {
     const std::vector<double>& f = ref.field(which);
     const std::vector<double>& h = u[which == 0 ? cur : old];
@@ -316,6 +343,14 @@ int main() {
                                    {20, 21, 21}, {20, 20, 20}, {10, 20, 20}, {11, 5, 5}};
     check_split("cube", 40, 12, false, 0.005, s40, {5, 5, 1});
     check_split("box", 40, 12, true, 0.005, s40, {5, 5, 1});
+    // tests/long_reference.py long_shot(40, box): K = 203 at 0.9 tau_max, 40 passes of 5 steps and one of 2 (the long
+    // fused GPU solves' configurations, tests/test_gpu_long_solves.py)
+    std::vector<int> split203(40, 5);
+    split203.push_back(2);
+    for (bool box : {false, true}) {
+      const double tau = 0.9 * make(40, 203, box).tau_max();
+      check_split(box ? "long-box" : "long-cube", 40, 203, box, tau, {Node{19, 20, 21}, Node{21, 19, 20}}, split203, true);
+    }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "unexpected exception: %s\n", e.what());
     return 2;

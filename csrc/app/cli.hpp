@@ -93,6 +93,10 @@ std::string jnum(double v);
 // empty for a cube, whose lines stay what they were
 std::string box_banner(const Problem& p);
 std::string box_json(const Problem& p);
+// sponge layers for the JSON summaries (", \"sponge\": [width, sigma, faces]"); empty without a sponge
+std::string sponge_json(const Problem& p);
+// --sponge: says once on stderr that the error columns have no meaning (nothing without a sponge)
+void sponge_notice(const Problem& p);
 // --energy: the line printed after the error log, and the two keys it adds to --json
 void print_energy(double e_start, double e_end);
 std::string energy_json(double e_start, double e_end);

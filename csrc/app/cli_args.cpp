@@ -116,6 +116,9 @@ constexpr Personality kPersonalities[] = {
                "                     (a node strictly inside the grid; a Ricker wavelet of peak frequency f0 centred at\n"
                "                     t0). The error lines then have no meaning. One GPU rank, --group (loopback,\n"
                "                     rccl-self) or --cpu; combines with --receivers, --box, --initial; not with --resume\n"
+               "  --sponge W[,SIGMA[,FACES]]  absorbing sponge layers of W nodes next to the faces FACES, a subset of the\n"
+               "                     letters xXyYzZ (lower case: the low face; default all six), peak damping rate SIGMA\n"
+               "                     (default 3 ln(1000) / (2 W h)). One GPU rank or --cpu. The error lines then have no meaning\n"
                "  --force            run even if the CFL condition is violated\n"
                "  --quiet            only the summary\n");
   std::exit(2);
@@ -232,6 +235,41 @@ Args parse(int argc, char** argv) {
       a.box[2] = e[2];
       a.have_box = true;
     }
+    else if (s == "--sponge") {
+      const std::string v = next();  // W[,SIGMA[,FACES]]; an empty SIGMA selects the default
+      std::string part[3];
+      size_t at = 0;
+      int n = 0;
+      for (; n < 3; ++n) {
+        const size_t c = v.find(',', at);
+        part[n] = v.substr(at, c == std::string::npos ? std::string::npos : c - at);
+        if (c == std::string::npos) break;
+        at = c + 1;
+      }
+      if (n == 3) usage("--sponge expects W[,SIGMA[,FACES]]");
+      Sponge sp;
+      try {
+        size_t used = 0;
+        sp.width = std::stoi(part[0], &used);
+        if (used != part[0].size()) throw std::invalid_argument(part[0]);
+        if (!part[1].empty()) {
+          sp.sigma = std::stod(part[1], &used);
+          if (used != part[1].size()) throw std::invalid_argument(part[1]);
+        }
+      } catch (const std::exception&) {
+        usage("--sponge expects W[,SIGMA[,FACES]]: an integer width and an optional number");
+      }
+      if (n == 2) {
+        if (part[2].empty()) usage("--sponge: FACES is empty (leave the last comma out for all six faces)");
+        sp.faces = 0;
+        for (char ch : part[2]) {
+          const size_t bit = std::string("xXyYzZ").find(ch);
+          if (bit == std::string::npos) usage("--sponge: FACES is a subset of the letters xXyYzZ");
+          sp.faces |= 1 << bit;
+        }
+      }
+      a.prob.sponge = sp;
+    }
     else if (s == "--force") a.force = true;
     else if (s == "--quiet") a.quiet = true;
     else if (s == "-h" || s == "--help") usage();
@@ -267,6 +305,8 @@ Args parse(int argc, char** argv) {
   if (!a.sources.empty() && a.np > 1)
     usage("--sources: one rank only (ranks of a multi-process world are not supported)");
   if (!a.sources.empty() && (a.serve || a.fake_rank >= 0)) usage("--sources: not with --serve or --fake-rank");
+  if (a.prob.sponge.on() && (a.np > 1 || a.group > 0 || a.serve || a.fake_rank >= 0))
+    usage("sponge: one rank only (not with --np, --group, --serve or --fake-rank)");
   if (a.repeat < 1) a.repeat = 1;
   return a;
 }
@@ -301,6 +341,16 @@ std::string box_banner(const Problem& p) {
 std::string box_json(const Problem& p) {
   if (!p.is_box()) return "";
   return ", \"box\": [" + jexact(p.L) + ", " + jexact(p.edge_y()) + ", " + jexact(p.edge_z()) + "]";
+}
+std::string sponge_json(const Problem& p) {
+  if (!p.sponge.on()) return "";
+  return ", \"sponge\": [" + std::to_string(p.sponge.width) + ", " + jexact(p.sponge.sigma) + ", " +
+         std::to_string(p.sponge.faces) + "]";
+}
+void sponge_notice(const Problem& p) {
+  if (p.sponge.on())
+    std::fprintf(stderr, "wave3d: sponge layers are set: the error columns compare with the undamped eigenmode and have "
+                         "no meaning\n");
 }
 void print_energy(double e_start, double e_end) {
   std::printf("Energy: E(1/2) = %.15e, E(K-1/2) = %.15e, drift = %.3e\n", e_start, e_end,

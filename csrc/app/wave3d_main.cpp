@@ -203,7 +203,7 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
   if (!a.json.empty()) {
     std::vector<int> cc = g.comm_counts();
     std::ofstream j(a.json);
-    j << "{\"backend\": \"hip\", \"group\": " << a.group << box_json(a.prob) << ", \"transport\": " << jstr(a.group_transport)
+    j << "{\"backend\": \"hip\", \"group\": " << a.group << box_json(a.prob) << sponge_json(a.prob) << ", \"transport\": " << jstr(a.group_transport)
       << ", \"graph\": " << (g.graph_enabled() ? "true" : "false") << ", \"schedule\": " << jstr(g.rank(0).mode())
       << ", \"temporal\": " << g.rank(0).options().temporal << ", \"stored_prev\": "
       << (g.rank(0).stored_prev() ? "true" : "false") << ", \"rccl_comms\": " << cc.size() << ", \"solve_s\": " << jnum(best);
@@ -443,7 +443,7 @@ int run_gpu(const Args& a) {
     if (!a.json.empty()) {
       std::ofstream j(a.json);
       j << "{\"backend\": \"hip\", \"N\": " << a.prob.N << ", \"tau\": " << jnum(a.prob.tau) << ", \"K\": " << a.prob.K
-        << ", \"L\": " << jnum(a.prob.L) << box_json(a.prob) << ", \"ranks\": " << world << ", \"dims\": [" << d.px << ", " << d.py
+        << ", \"L\": " << jnum(a.prob.L) << box_json(a.prob) << sponge_json(a.prob) << ", \"ranks\": " << world << ", \"dims\": [" << d.px << ", " << d.py
         << ", " << d.pz << "], \"solve_s\": " << jnum(best) << ", \"mean_s\": " << jnum(mean)
         << ", \"first_s\": " << jnum(first) << ", \"process_s\": " << jnum(t_proc) << ", \"rccl_init_s\": "
         << jnum(t_comm) << ", \"rccl_nranks\": " << rccl_nranks << ", \"rccl_version\": " << rccl_version()
@@ -539,6 +539,9 @@ int main(int argc, char** argv) {
       group = std::make_unique<ShmGroup>(a.prob, parse_dims(a.decomp, lworld, a.prob.N), lworld, job_segment_name(),
                                          cpu_rank);
     }
+    W3D_REQUIRE(!a.prob.sponge.on() || (!group && lworld <= 1),
+                "sponge: one rank only (ranks of a multi-process world are not supported)");
+    sponge_notice(a.prob);
     W3D_REQUIRE(a.sources.empty() || (!group && lworld <= 1),
                 "sources: one rank only (ranks of a multi-process world are not supported)");
     W3D_REQUIRE(a.receivers.empty() || (!group && lworld <= 1),

@@ -151,8 +151,59 @@ inline double energy_value(const Problem& p, double kin, double pot) {
 
 // u^{n+1} = 2u^n − u^{n−1} + τ²Δ_h u^n on `box`, written in place over u^{n−1} (`old_out`).
 // If acc != nullptr also accumulates the error vs the analytic solution φ·ct over the box.
+// sponge != nullptr: the damped update (stencil.hpp leapfrog_damped) with the node's g = max, r = min of the three 1-D
+// tables (problem.hpp sponge_tables; global indices); a node with g = 0 gets the undamped bits.
 void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox& box,
-                  const double* s, double ct, ErrAcc* acc);
+                  const double* s, double ct, ErrAcc* acc, const SpongeView* sponge = nullptr);
+
+// Sponge layers and the fused passes. An undamped pass of `steps` steps from damped levels u^{n−1}, u^n differs from
+// the damped one only within reach of the layers: u^{n+steps} on the slabs d < W + steps − 1 from each damped face (d:
+// nodes from the face), u^{n+steps−1} on d < W + steps − 2. sponge_boxes returns disjoint local boxes whose union is
+// exactly the union of the slabs d < W + steps − 1, clipped to the interior, with opposite slabs merged where they
+// meet; cut as shell_split cuts: x slabs whole, y slabs inside the remaining x range, z slabs inside both (≤ 6 boxes).
+// reach = W + steps − 1 for the default; sponge_reach_boxes takes the reach itself.
+inline std::vector<LBox> sponge_reach_boxes(const Problem& p, const Layout& l, i64 reach) {
+  std::vector<LBox> out;
+  if (!p.sponge.on() || reach <= 0) return out;
+  const i64 N = p.N;
+  // per axis: the damped intervals [a0, a1) ∪ [b0, b1) of global nodes and the interval [c0, c1) between them
+  i64 iv[3][2][2], mid[3][2];
+  for (int a = 0; a < 3; ++a) {
+    const bool lo = (p.sponge.faces >> (2 * a)) & 1, hi = (p.sponge.faces >> (2 * a + 1)) & 1;
+    i64 a1 = lo ? imin(reach, N) : 1;       // low slab: nodes 1 .. reach − 1
+    i64 b0 = hi ? imax(N - reach + 1, 1) : N;  // high slab: nodes N − reach + 1 .. N − 1
+    if (lo && hi && a1 >= b0) {  // the two slabs meet: one interval
+      a1 = N;
+      b0 = N;
+    }
+    b0 = imax(b0, a1);
+    iv[a][0][0] = 1;
+    iv[a][0][1] = a1;
+    iv[a][1][0] = b0;
+    iv[a][1][1] = N;
+    mid[a][0] = a1;
+    mid[a][1] = b0;
+  }
+  const i64 g0[3] = {l.gx0, l.gy0, l.gz0};
+  auto push = [&](const i64 r[3][2]) {
+    const LBox b{r[0][0] - g0[0], r[0][1] - g0[0], r[1][0] - g0[1], r[1][1] - g0[1], r[2][0] - g0[2], r[2][1] - g0[2]};
+    if (!b.empty()) out.push_back(b);
+  };
+  for (int a = 0; a < 3; ++a)
+    for (int side = 0; side < 2; ++side) {
+      i64 r[3][2];
+      for (int b = 0; b < 3; ++b) {
+        // earlier axes: the range their slabs left; this axis: the slab; later axes: the whole interior
+        r[b][0] = b < a ? mid[b][0] : (b == a ? iv[a][side][0] : 1);
+        r[b][1] = b < a ? mid[b][1] : (b == a ? iv[a][side][1] : N);
+      }
+      push(r);
+    }
+  return out;
+}
+inline std::vector<LBox> sponge_boxes(const Problem& p, const Layout& l, int steps) {
+  return sponge_reach_boxes(p, l, static_cast<i64>(p.sponge.width) + steps - 1);
+}
 
 // Point sources u_tt = Δu + Σ_q w_q(t) δ(x − x_q), δ discretised as 1/(hx·hy·hz) at the node: the addend of sample w at
 // a source node is a = τ²·w / (hx·hy·hz), evaluated by this one expression on every backend. The first level gets ½·a⁰
@@ -208,6 +259,9 @@ class CpuSolver {
  public:
   CpuSolver(const Problem& p, int check_every = 2, int threads = 0);
   CpuResult run();
+  // With Problem::sponge set every step is the damped one (stencil.hpp leapfrog_damped); the start levels, set_initial,
+  // set_state, receivers, sources (added after the damped step, as after the plain one) and energy work as before. The
+  // error columns then have no meaning, and the energy decays.
   // Start every following run() at step n0 from u^{n0−1} = prev and u^{n0} = cur (global (N+1)³ fields) instead of
   // the analytic initial condition: the leapfrog continues to K and checks the steps after n0.
   void set_state(const double* prev_global, const double* cur_global, int n0);
@@ -245,6 +299,7 @@ class CpuSolver {
   Layout lay_;
   std::vector<double> u_[2];
   std::vector<double> s_;
+  SpongeTables sponge_;                  // Problem::sponge's coefficient tables (empty: no sponge)
   int final_ = 1;
   int resume_n_ = 0;                     // > 0: start step of a resumed run
   std::vector<double> resume_[2];        // local u^{n0−1}, u^{n0}

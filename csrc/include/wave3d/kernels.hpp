@@ -86,8 +86,22 @@ void launch_source_cone(const Layout& l, const Coeffs& c, double* out_prev, doub
 
 // Runs one leapfrog step over up to 6 boxes in a single launch. If `partials` is non-null the error vs φ·ct is reduced
 // per workgroup into partials[0 .. leapfrog_blocks()).
+// sponge != nullptr: the damped step of the sponge layers (the DAMP instantiations; the tables live in device memory,
+// problem.hpp SpongeView); bit-identical to cpu_leapfrog with the same tables.
 void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox* boxes, int nbox,
-                     const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream);
+                     const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream,
+                     const SpongeView* sponge = nullptr);
+
+// Sponge layers on the fused schedule (kernels_sponge.hip). An LDS pass of `steps` steps runs undamped; its two stored
+// outputs differ from the damped levels only on the slabs cpu.hpp sponge_boxes returns, which this recomputes from the
+// pass's INPUTS prev = u^{n−1}, cur = u^n with the damped operator: it writes out2 = u^{n+steps} and out1 =
+// u^{n+steps−1} on `box` (steps = 2..5), bit-identical to `steps` damped cpu_leapfrog steps. It reads the inputs on `box`
+// grown by `steps` and clipped to the domain, never addresses a node on or outside the global boundary (those count
+// as +0.0) and writes nothing outside `box`. One rank that spans the whole domain; four distinct buffers; `tables` in
+// device memory. sponge_box_prepare raises the kernels' dynamic-LDS limit (call before capturing a launch).
+void sponge_box_prepare();
+void launch_sponge_box(const Layout& l, const Coeffs& c, const SpongeView& tables, const double* prev, const double* cur,
+                       double* out1, double* out2, const LBox& box, int steps, hipStream_t stream);
 
 // Temporal blocking: TWO leapfrog steps in one pass over HBM (u^{n+1}, u^{n+2} from u^{n−1}, u^n), 16 instead of
 // 24 compulsory bytes per node-step. Needs every node of `box` to be updatable without a halo exchange (single rank:

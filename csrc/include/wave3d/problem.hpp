@@ -12,11 +12,22 @@
 #pragma once
 
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "wave3d/common.hpp"
 
 namespace wave3d {
+
+// Absorbing sponge layer next to a subset of the six faces: u_tt + 2σ(x)u_t = Δu with σ > 0 only inside the layer
+// (sponge_tables below has the profile; stencil.hpp::leapfrog_damped the update). width = 0 or faces = 0: no sponge, and
+// nothing anywhere changes.
+struct Sponge {
+  int width = 0;       // W: nodes 1 .. W−1 from a damped face are damped
+  double sigma = 0.0;  // peak damping rate; ≤ 0: the default 3·ln(1000)/(2·W·h_a) per axis
+  int faces = 63;      // bits 0..5: x−, x+, y−, y+, z−, z+
+  bool on() const { return width > 0 && (faces & 63) != 0; }
+};
 
 struct Problem {
   i64 N = 512;        // number of intervals per axis → (N+1)^3 nodes
@@ -25,6 +36,7 @@ struct Problem {
   double L = 1.0;     // edge length in x (Lx); a cube's only edge
   double Ly = 0.0;    // edge lengths in y and z of a rectangular box; ≤ 0: "= L"
   double Lz = 0.0;
+  Sponge sponge;      // absorbing layers (off by default)
 
   double Lx() const { return L; }
   double edge_y() const { return Ly > 0.0 ? Ly : L; }
@@ -62,6 +74,13 @@ struct Problem {
     W3D_REQUIRE(K >= 1, "K must be >= 1");
     W3D_REQUIRE(L > 0.0 && std::isfinite(L), "L must be > 0");
     W3D_REQUIRE(std::isfinite(Ly) && std::isfinite(Lz), "box edges must be finite");
+    W3D_REQUIRE(sponge.width >= 0, "sponge: the width must be >= 0");
+    W3D_REQUIRE(!sponge.on() || 2 * static_cast<i64>(sponge.width) <= N - 1,
+                "sponge: two layers of width " + std::to_string(sponge.width) + " do not fit into the " +
+                    std::to_string(N - 1) + " interior nodes of an axis (2 * width <= N - 1)");
+    W3D_REQUIRE(std::isfinite(sponge.sigma) && (sponge.sigma >= 0.0 || !sponge.on()),
+                "sponge: sigma must be finite and >= 0 (0 selects the default)");
+    W3D_REQUIRE(sponge.faces >= 0 && sponge.faces <= 63, "sponge: faces is a mask of bits 0..5 (x-, x+, y-, y+, z-, z+)");
   }
 };
 
@@ -114,6 +133,51 @@ inline std::vector<double> sin_table_ext(const Problem& p) {
     s[static_cast<size_t>(i + 1)] = std::sin(M_PI * x / p.L);
   }
   return s;  // s[1] (node 0) and s[N+1] (node N) stay exact zeros
+}
+
+// Sponge coefficients. For a node d nodes from a damped face of axis a, 1 ≤ d < W, the 1-D value is
+//   g_a = (τ·sigma_a)·(q·q),  q = (W − d)/W      (a quadratic ramp; 0 for d ≥ W and on or outside the boundary),
+// the larger of the two where both faces of the axis reach the node, and r_a = 1.0/(1.0 + g_a) entry by entry. Default
+// sigma_a = 3·ln(1000)/(2·W·h_a): the continuous two-way amplitude reflection 1e-3 of a quadratic profile at c = 1.
+// Each table is extended by one entry on each side like sin_table_ext: element [i + 1] holds node i = −1..N+1. A node's
+// coefficients are g = fmax(fmax(gx[i], gy[j]), gz[k]) and r = fmin(fmin(rx[i], ry[j]), rz[k]) — no division and no
+// rounding where they are used, and r belongs to the same entry as g because 1/(1 + g) is monotone.
+struct SpongeView {  // pointers to node 0 of the six tables (host or device), indexable −1..N+1
+  const double *gx = nullptr, *gy = nullptr, *gz = nullptr, *rx = nullptr, *ry = nullptr, *rz = nullptr;
+};
+struct SpongeTables {
+  std::vector<double> g[3], r[3];  // N + 3 entries each
+  SpongeView view() const {
+    return SpongeView{g[0].data() + 1, g[1].data() + 1, g[2].data() + 1, r[0].data() + 1, r[1].data() + 1, r[2].data() + 1};
+  }
+};
+inline double sponge_sigma(const Problem& p, int axis) {
+  if (p.sponge.sigma > 0.0) return p.sponge.sigma;
+  const double h = axis == 0 ? p.hx() : (axis == 1 ? p.hy() : p.hz());
+  return (3.0 * std::log(1000.0)) / ((2.0 * static_cast<double>(p.sponge.width)) * h);
+}
+inline SpongeTables sponge_tables(const Problem& p) {
+  SpongeTables t;
+  const i64 W = p.sponge.width;
+  for (int a = 0; a < 3; ++a) {
+    t.g[a].assign(static_cast<size_t>(p.N + 3), 0.0);
+    t.r[a].assign(static_cast<size_t>(p.N + 3), 1.0);
+    if (!p.sponge.on()) continue;
+    const double ts = p.tau * sponge_sigma(p, a);
+    const bool lo = (p.sponge.faces >> (2 * a)) & 1, hi = (p.sponge.faces >> (2 * a + 1)) & 1;
+    for (i64 i = 1; i < p.N; ++i) {
+      double g = 0.0;
+      for (int side = 0; side < 2; ++side) {
+        const i64 d = side == 0 ? i : p.N - i;
+        if (!(side == 0 ? lo : hi) || d >= W) continue;
+        const double q = static_cast<double>(W - d) / static_cast<double>(W);
+        g = std::fmax(g, ts * (q * q));
+      }
+      t.g[a][static_cast<size_t>(i + 1)] = g;
+      t.r[a][static_cast<size_t>(i + 1)] = 1.0 / (1.0 + g);
+    }
+  }
+  return t;
 }
 
 // cos(a_t · n · τ): the time factor of the analytic solution at step n.

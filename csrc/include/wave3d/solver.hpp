@@ -156,6 +156,16 @@ class GpuSolver {
   // is not argued for it), ranks of a multi-process world, and set_state together with sources.
   void set_sources(const i64* ijk, int Q, const double* w);
   int sources() const { return n_src_; }
+  // Sponge layers (Problem::sponge; cpu.hpp CpuSolver is the definition, the fields match it bit for bit). The LDS pass
+  // kernels are untouched: every fused unit runs undamped and is followed, on s0, by k_sponge_box launches that recompute
+  // the slabs within reach of the layers (cpu.hpp sponge_boxes) from the unit's inputs with the damped operator and store
+  // both levels over the pass's outputs; single-step units run the DAMP instantiations of the single-step kernels. The
+  // start levels are stored (no analytic start, no init2) and the last pass keeps both levels (no drop_prev). Nothing on
+  // the host per solve: the solve stays graph-captured and run_batch pipelined. The error log then has no meaning.
+  // Refused (messages start with "sponge:"): a world larger than 1 of any kind, fake ranks, the push and copy-engine
+  // transports, tb = false (k_leapfrog2 pairs), and a receiver or source within W + temporal nodes of a damped face (the
+  // cone kernels recompute with the undamped operator, which equals the damped one only outside that reach).
+  bool sponge() const { return sch_.prob.sponge.on(); }
   // Discrete energy (cpu.hpp cpu_energy): which = 0: E^{K−1/2} of the retained u^{K−1}, u^K; which = 1: E^{1/2},
   // computed inside the solve right after the first-step kernel (solves started by set_initial) and kept on the
   // device. One rank only. energy_sums: the kinetic and potential sums themselves.
@@ -330,6 +340,13 @@ class GpuSolver {
   // u^{n+s}, on s0
   void source_correct(const UnitPlan* u, double* prev, double* last);
   void source_finish();  // end of the solve: the last unit's correction
+  double* sponge_dev_ = nullptr;      // sponge layers: the six tables (N + 3 entries each) in device memory ...
+  SpongeView sponge_view_;            // ... and their node-0 pointers
+  std::vector<LBox> sponge_boxes_[6]; // ... and the slabs a fused unit of s = 2..5 steps recomputes (cpu.hpp sponge_boxes)
+  const SpongeView* sponge_arg() const { return sponge() ? &sponge_view_ : nullptr; }
+  void sponge_unit(const UnitPlan& u);  // after a fused unit's pass, on s0: the slabs of its two outputs, damped
+  // a receiver or a source's ball must stay out of the layers' reach (refusal; `what` names the list)
+  void sponge_check_nodes(const i64* ijk, int n, const char* what) const;
   mutable Partial* energy_part_ = nullptr;  // k_energy's partials, then [n] = E^{K−1/2}'s sums, [n + 1] = E^{1/2}'s
   void energy_alloc() const;
   void drop_graphs();

@@ -66,6 +66,21 @@ W3D_HD double leapfrog(double c, double old, double s, double lam) {
 #endif
 }
 
+// Damped leapfrog (sponge layers): u_tt + 2σu_t = Δu with u_t centred in time, (1 + g)·u^{n+1} = 2u^n − (1 − g)·u^{n−1} +
+// τ²Δ_h u^n, g = σ(x)·τ ≥ 0. With w = leapfrog(c, old, s, lam), exactly the undamped value, u^{n+1} = (w + g·old)/(1 + g) =
+// fma(g, old, w)·r with r = 1.0/(1.0 + g) tabulated (problem.hpp sponge_tables). Where g == 0 the result is w itself,
+// not the damped expression fed a zero: a node outside the sponge gets the undamped bits by construction. Von Neumann:
+// (1 + g)z² − (2 − λ)z + (1 − g) = 0 with λ ∈ [0, 4] under the undamped CFL limit has |z₁z₂| = (1 − g)/(1 + g) ≤ 1 and,
+// for real roots, |z₁ + z₂| = |2 − λ|/(1 + g) ≤ 1 + z₁z₂ = 2/(1 + g): both roots in the closed unit disc for every g ≥ 0,
+// so the damping costs no time step.
+W3D_HD double leapfrog_damped(double w, double old, double g, double r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return g > 0.0 ? __builtin_fma(g, old, w) * r : w;
+#else
+  return g > 0.0 ? std::fma(g, old, w) * r : w;
+#endif
+}
+
 // Second-order first step u^1 = u^0 + τ²/2 Δ_h u^0, using ∂u/∂t = 0 (report.pdf p.5 §2.2(2)); half_lam = τ²/(2h²).
 // (fused like leapfrog)
 W3D_HD double first_step(double c, double s, double half_lam) {

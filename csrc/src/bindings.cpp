@@ -130,8 +130,15 @@ py::dict result_dict(const RunResult& r) {
 PYBIND11_MODULE(_C, m) {
   m.doc() = "wave3d native runtime: CDNA4 HIP kernels, RCCL halo exchange, CPU/OpenMP path";
 
+  py::class_<Sponge>(m, "Sponge")
+      .def(py::init([](int width, double sigma, int faces) { return Sponge{width, sigma, faces}; }),
+           py::arg("width") = 0, py::arg("sigma") = 0.0, py::arg("faces") = 63)
+      .def_readwrite("width", &Sponge::width)
+      .def_readwrite("sigma", &Sponge::sigma)
+      .def_readwrite("faces", &Sponge::faces)
+      .def_property_readonly("on", &Sponge::on);
   py::class_<Problem>(m, "Problem")
-      .def(py::init([](i64 N, double tau, int K, double L, double Ly, double Lz) {
+      .def(py::init([](i64 N, double tau, int K, double L, double Ly, double Lz, const Sponge& sponge) {
              Problem p;
              p.N = N;
              p.tau = tau;
@@ -139,11 +146,14 @@ PYBIND11_MODULE(_C, m) {
              p.L = L;
              p.Ly = Ly;
              p.Lz = Lz;
+             p.sponge = sponge;
              p.validate();
              return p;
            }),
            py::arg("N") = 512, py::arg("tau") = 1e-3, py::arg("K") = 20, py::arg("L") = 1.0, py::kw_only(),
-           py::arg("Ly") = 0.0, py::arg("Lz") = 0.0)
+           py::arg("Ly") = 0.0, py::arg("Lz") = 0.0, py::arg("sponge") = Sponge{})
+      .def_readwrite("sponge", &Problem::sponge)
+      .def("validate", &Problem::validate)
       .def_readwrite("N", &Problem::N)
       .def_readwrite("tau", &Problem::tau)
       .def_readwrite("K", &Problem::K)
@@ -186,6 +196,17 @@ PYBIND11_MODULE(_C, m) {
     return darr(static_cast<py::ssize_t>(v.size()), v.data());
   });
   m.def("time_factor", &time_factor);
+  m.def("sponge_tables", [](const Problem& p) {
+    const SpongeTables t = sponge_tables(p);
+    const py::ssize_t n = static_cast<py::ssize_t>(p.N + 3);
+    darr out({static_cast<py::ssize_t>(6), n});
+    for (int a = 0; a < 3; ++a) {
+      std::memcpy(out.mutable_data(a), t.g[a].data(), static_cast<size_t>(n) * sizeof(double));
+      std::memcpy(out.mutable_data(3 + a), t.r[a].data(), static_cast<size_t>(n) * sizeof(double));
+    }
+    return out;
+  }, "the sponge coefficient tables as rows (gx, gy, gz, rx, ry, rz) of N + 3 entries: element [i + 1] = node i");
+  m.def("sponge_sigma", &sponge_sigma, py::arg("problem"), py::arg("axis"));
   // elementwise IEEE fused multiply-add (the rounding of stencil.hpp's leapfrog / first_step / err_sq_acc), for the
   // numpy emulators that must reproduce the kernels bit for bit (numpy has no fma)
   m.def("fma_array", [](const darr& a, const darr& b, const darr& c) {
@@ -295,6 +316,8 @@ PYBIND11_MODULE(_C, m) {
       .def("count", &LBox::count)
       .def("as_tuple", [](const LBox& b) { return py::make_tuple(b.x0, b.x1, b.y0, b.y1, b.z0, b.z1); });
   m.def("compute_box", &compute_box);
+  m.def("sponge_boxes", &sponge_boxes, py::arg("problem"), py::arg("layout"), py::arg("steps"),
+        "disjoint boxes whose union is the slabs d < W + steps - 1 from the damped faces, clipped to the interior");
   m.def("plan_receivers",
         [](const Problem& p, const Dims& d, int rank, const Layout& l, const iarr& nodes) {
           const std::vector<Receiver> v = plan_receivers(p, d, rank, l, receiver_nodes(nodes));
@@ -411,20 +434,26 @@ PYBIND11_MODULE(_C, m) {
   m.def(
       "cpu_leapfrog",
       [](const Layout& l, const Coeffs& c, const darr& cur, darr old, const LBox& box, const darr& s, double ct,
-         bool check) -> py::object {
+         bool check, py::object sponge) -> py::object {
         const double* cp = ro_ptr(cur, l.total, "cur");
         double* op = mut_ptr(old, l.total, "old");
         const double* sp = ro_ptr(s, l.N + 3, "s") + 1;
+        SpongeTables tab;  // sponge: a Problem whose sponge_tables give the damped step
+        SpongeView view;
+        if (!sponge.is_none()) {
+          tab = sponge_tables(sponge.cast<Problem>());
+          view = tab.view();
+        }
         ErrAcc acc;
         {
           py::gil_scoped_release nogil;
-          cpu_leapfrog(l, c, cp, op, box, sp, ct, check ? &acc : nullptr);
+          cpu_leapfrog(l, c, cp, op, box, sp, ct, check ? &acc : nullptr, sponge.is_none() ? nullptr : &view);
         }
         if (!check) return py::none();
         return py::make_tuple(acc.max, acc.sum);
       },
       py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("old"), py::arg("box"), py::arg("s"),
-      py::arg("ct") = 0.0, py::arg("check") = false);
+      py::arg("ct") = 0.0, py::arg("check") = false, py::arg("sponge") = py::none());
   m.def("cpu_error", [](const Layout& l, const darr& u, const LBox& box, const darr& s, double ct) {
     ErrAcc acc;
     cpu_error(l, ro_ptr(u, l.total, "u"), box, ro_ptr(s, l.N + 3, "s") + 1, ct, &acc);
@@ -491,7 +520,16 @@ PYBIND11_MODULE(_C, m) {
         s.set_sources(nodes.data(), Q, wp);
       }, py::arg("nodes"), py::arg("w"), "point sources at these (Q, 3) global nodes with the (K, Q) samples w")
       .def_property_readonly("sources", &CpuSolver::sources)
-      .def("energy", &CpuSolver::energy, py::arg("which") = 0);
+      .def("energy", &CpuSolver::energy, py::arg("which") = 0)
+      .def("energy_sums", [](const CpuSolver& s, int which) {
+             const EnergySums e = s.energy_sums(which);
+             py::dict d;
+             d["kin"] = e.kin;
+             d["pot"] = e.pot;
+             d["abs"] = e.abs;
+             d["depth"] = e.depth;
+             return d;
+           }, py::arg("which") = 0, "the sums behind energy(which): kin, pot, abs (the summation-error scale), depth");
 
   // ---------------- GPU ----------------
   m.def("gpu_device_count", []() {
@@ -607,11 +645,35 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("gpu_leapfrog",
         [](const Layout& l, const Coeffs& c, std::uintptr_t cur, std::uintptr_t old, const std::vector<LBox>& boxes,
-           std::uintptr_t s, double ct, std::uintptr_t partials, const LeapfrogTiling& t, std::uintptr_t stream) {
+           std::uintptr_t s, double ct, std::uintptr_t partials, const LeapfrogTiling& t, std::uintptr_t stream,
+           std::uintptr_t sponge) {
+          // sponge: sponge_tables' (6, N + 3) array in device memory (0: the undamped step)
+          SpongeView view;
+          if (sponge) {
+            const i64 n = l.N + 3;
+            const double* g = dptr<const double>(sponge);
+            view = SpongeView{g + 1, g + n + 1, g + 2 * n + 1, g + 3 * n + 1, g + 4 * n + 1, g + 5 * n + 1};
+          }
           launch_leapfrog(l, c, dptr<const double>(cur), dptr<double>(old), boxes.data(),
                           static_cast<int>(boxes.size()), dptr<const double>(s) + 1, ct, dptr<Partial>(partials), t,
-                          sptr(stream));
-        });
+                          sptr(stream), sponge ? &view : nullptr);
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("old"), py::arg("boxes"), py::arg("s"),
+        py::arg("ct"), py::arg("partials"), py::arg("tiling"), py::arg("stream"), py::arg("sponge") = 0);
+  m.def("gpu_sponge_box",
+        [](const Layout& l, const Coeffs& c, std::uintptr_t tables, std::uintptr_t prev, std::uintptr_t cur,
+           std::uintptr_t out1, std::uintptr_t out2, const LBox& box, int steps, std::uintptr_t stream) {
+          const i64 n = l.N + 3;
+          const double* g = dptr<const double>(tables);
+          W3D_REQUIRE(g != nullptr, "sponge_box: no tables");
+          const SpongeView view{g + 1, g + n + 1, g + 2 * n + 1, g + 3 * n + 1, g + 4 * n + 1, g + 5 * n + 1};
+          launch_sponge_box(l, c, view, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
+                            dptr<double>(out2), box, steps, sptr(stream));
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("tables"), py::arg("prev"), py::arg("cur"), py::arg("out1"),
+        py::arg("out2"), py::arg("box"), py::arg("steps"), py::arg("stream"),
+        "k_sponge_box: out2 = u^{n+steps}, out1 = u^{n+steps-1} on `box` by `steps` damped steps from prev, cur; "
+        "tables: sponge_tables' (6, N + 3) array in device memory");
   py::class_<Leapfrog2Tiling>(m, "Leapfrog2Tiling")
       .def(py::init<>())
       .def_readwrite("rows", &Leapfrog2Tiling::rows)
@@ -900,6 +962,7 @@ PYBIND11_MODULE(_C, m) {
         s.set_sources(nodes.data(), Q, wp);
       }, py::arg("nodes"), py::arg("w"), "point sources at these (Q, 3) global nodes with the (K, Q) samples w")
       .def_property_readonly("sources", &GpuSolver::sources)
+      .def_property_readonly("sponge", &GpuSolver::sponge)
       .def("energy", &GpuSolver::energy, py::arg("which") = 0,
            "discrete energy E^{K-1/2} (which = 0) / E^{1/2} (which = 1, after set_initial); one rank only")
       .def("energy_sums", [](const GpuSolver& s, int which) {

@@ -136,9 +136,9 @@ EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double
 
 namespace {
 
-template <bool CHECK, bool BOX>
+template <bool CHECK, bool BOX, bool DAMP = false>
 void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* out, const LBox& b, const double* s,
-                   double ct, ErrAcc* acc) {
+                   double ct, ErrAcc* acc, const SpongeView* sp = nullptr) {
   const i64 nxp = b.x1 - b.x0;
   std::vector<ErrAcc> part(CHECK ? static_cast<size_t>(nxp) : 0);
   const i64 P = l.plane, R = l.pitch;
@@ -146,8 +146,10 @@ void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* 
   for (i64 ix = b.x0; ix < b.x1; ++ix) {
     double emax = 0.0, esum = 0.0;
     const double sx = s[l.gx0 + ix];
+    const double gx = DAMP ? sp->gx[l.gx0 + ix] : 0.0, rx = DAMP ? sp->rx[l.gx0 + ix] : 1.0;
     for (i64 iy = b.y0; iy < b.y1; ++iy) {
       const double sxy = analytic_row(sx, s[l.gy0 + iy], ct);
+      const double gxy = DAMP ? std::fmax(gx, sp->gy[l.gy0 + iy]) : 0.0, rxy = DAMP ? std::fmin(rx, sp->ry[l.gy0 + iy]) : 1.0;
       const i64 row = l.off(ix, iy, 0);
       const double* cr = cur + row;
       double* orow = out + row;
@@ -155,7 +157,8 @@ void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* 
         const double u = cr[iz];
         const double lap = d2sum_t<BOX>(u, cr[iz - P], cr[iz + P], cr[iz - R], cr[iz + R], cr[iz - 1], cr[iz + 1],
                                         c.ry, c.rz);
-        const double v = leapfrog(u, orow[iz], lap, c.lam);
+        double v = leapfrog(u, orow[iz], lap, c.lam);
+        if (DAMP) v = leapfrog_damped(v, orow[iz], std::fmax(gxy, sp->gz[l.gz0 + iz]), std::fmin(rxy, sp->rz[l.gz0 + iz]));
         orow[iz] = v;
         if (CHECK) {
           const double e = std::fabs(v - sxy * s[l.gz0 + iz]);
@@ -177,9 +180,20 @@ void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* 
 }  // namespace
 
 void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox& box,
-                  const double* s, double ct, ErrAcc* acc) {
+                  const double* s, double ct, ErrAcc* acc, const SpongeView* sponge) {
   if (box.empty()) return;
-  if (c.box) {  // (a rectangular box: stencil.hpp::d2sum_box)
+  if (sponge) {  // (sponge layers: the same loop with the damped update)
+    if (c.box) {
+      if (acc)
+        leapfrog_impl<true, true, true>(l, c, cur, old_out, box, s, ct, acc, sponge);
+      else
+        leapfrog_impl<false, true, true>(l, c, cur, old_out, box, s, ct, nullptr, sponge);
+    } else if (acc) {
+      leapfrog_impl<true, false, true>(l, c, cur, old_out, box, s, ct, acc, sponge);
+    } else {
+      leapfrog_impl<false, false, true>(l, c, cur, old_out, box, s, ct, nullptr, sponge);
+    }
+  } else if (c.box) {  // (a rectangular box: stencil.hpp::d2sum_box)
     if (acc)
       leapfrog_impl<true, true>(l, c, cur, old_out, box, s, ct, acc);
     else

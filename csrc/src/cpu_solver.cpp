@@ -24,6 +24,7 @@ CpuSolver::CpuSolver(const Problem& p, int check_every, int threads) : prob_(p),
   u_[0].assign(static_cast<size_t>(lay_.total), 0.0);
   u_[1].assign(static_cast<size_t>(lay_.total), 0.0);
   s_ = sin_table_ext(prob_);
+  if (prob_.sponge.on()) sponge_ = sponge_tables(prob_);
 }
 
 void global_to_local(const Layout& l, const double* g, double* out) {
@@ -161,6 +162,9 @@ CpuResult CpuSolver::run() {
   CpuResult r;
   const Coeffs c = Coeffs::from(prob_);
   const double* s = s_.data() + 1;
+  // sponge layers: every step is the damped one (cpu_leapfrog's table argument); the start levels are what they are
+  const SpongeView sponge_view = prob_.sponge.on() ? sponge_.view() : SpongeView{};
+  const SpongeView* sp = prob_.sponge.on() ? &sponge_view : nullptr;
   const LBox box = compute_box(lay_);
   const double n_int = static_cast<double>(prob_.N - 1);
   const double denom = n_int * n_int * n_int;
@@ -212,10 +216,10 @@ CpuResult CpuSolver::run() {
     const double tc = now_s();
     if (is_check[static_cast<size_t>(n + 1)]) {
       ErrAcc a;
-      cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, time_factor(prob_, n + 1), &a);
+      cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, time_factor(prob_, n + 1), &a, sp);
       record(n + 1, a);
     } else {
-      cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, 0.0, nullptr);
+      cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, 0.0, nullptr, sp);
     }
     r.compute_s += now_s() - tc;
     std::swap(cur, old);

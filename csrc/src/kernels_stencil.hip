@@ -130,11 +130,15 @@ struct LfParams {
   double ihx2, ihy2, ihz2, tau2, ct;
   // rectangular box: h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box; 1 for a cube — the same bits as d2sum)
   double ry, rz;
+  // sponge layers (the DAMP instantiations): the six 1-D tables in device memory, global node index −1..N+1
+  SpongeView sp;
   int nbox, ntiles, nblocks, xcd_remap;
   TileBox box[kMaxBoxes];
 };
 
-template <int TY, bool CHECK, bool NT>
+// DAMP: the damped update of the sponge layers (stencil.hpp leapfrog_damped). gx / rx of the plane are wave-uniform loads
+// issued one plane ahead like sxp; the thread's gy, ry and the gz, rz of its two nodes are loaded once before the march.
+template <int TY, bool CHECK, bool NT, bool DAMP = false>
 __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
   static_assert(TY >= 4, "halo slots need at least 128 + 2*TY threads");
   __shared__ v2d lds[2][TY + 2][kLanes + 2];
@@ -217,12 +221,22 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
     sz0 = p.s[p.gz0 + o0 - 1 - p.zs];
     sz1 = p.s[p.gz0 + o0 - p.zs];
   }
+  double gyz0 = 0.0, gyz1 = 0.0, ryz0 = 1.0, ryz1 = 1.0;  // max / min over the node's y and z entries
+  double gxp = DAMP ? p.sp.gx[p.gx0 + xs] : 0.0, rxp = DAMP ? p.sp.rx[p.gx0 + xs] : 1.0;
+  if (DAMP && active) {
+    const double gy = p.sp.gy[p.gy0 + y], ry = p.sp.ry[p.gy0 + y];
+    gyz0 = fmax(gy, p.sp.gz[p.gz0 + o0 - 1 - p.zs]);
+    gyz1 = fmax(gy, p.sp.gz[p.gz0 + o0 - p.zs]);
+    ryz0 = fmin(ry, p.sp.rz[p.gz0 + o0 - 1 - p.zs]);
+    ryz1 = fmin(ry, p.sp.rz[p.gz0 + o0 - p.zs]);
+  }
 
   for (i64 x = xs; x < xe; ++x, px += plane) {
     const int buf = static_cast<int>((x - xs) & 1);
     const bool more = x + 1 < xe;
     v2d nxt = zero2, uo_n = zero2, hv_n = zero2;
     const double nsxp = CHECK && more ? p.s[p.gx0 + x + 1] : 0.0;  // one plane ahead (in-order vmcnt)
+    const double ngxp = DAMP && more ? p.sp.gx[p.gx0 + x + 1] : 0.0, nrxp = DAMP && more ? p.sp.rx[p.gx0 + x + 1] : 1.0;
     if (more) {
       if (active) {
         nxt = ld2(cur + px + 2 * plane + my);
@@ -243,6 +257,10 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
       v2d r;
       r.x = leapfrog(uc.x, uo.x, l0, tau2);
       r.y = leapfrog(uc.y, uo.y, l1, tau2);
+      if (DAMP) {
+        r.x = leapfrog_damped(r.x, uo.x, fmax(gxp, gyz0), fmin(rxp, ryz0));
+        r.y = leapfrog_damped(r.y, uo.y, fmax(gxp, gyz1), fmin(rxp, ryz1));
+      }
       double* dst = out + px + my;
       if (ok0 && ok1)
         st2<NT>(dst, r);
@@ -270,6 +288,8 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
     uo = uo_n;
     hv = hv_n;
     sxp = nsxp;
+    gxp = ngxp;
+    rxp = nrxp;
   }
 
   if (CHECK) {
@@ -302,8 +322,11 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
 // many independent HBM streams stay in flight (R rows × 2 fields × 1 KiB per wave per plane).
 constexpr int kWavesRq = 4;  // waves per workgroup (scheduling only; they do not cooperate)
 
-template <int R, bool CHECK, bool NT>
-__global__ __launch_bounds__(64 * kWavesRq) __attribute__((amdgpu_waves_per_eu(R <= 2 ? 4 : 2))) void k_leapfrog_rq(
+template <int R, bool CHECK, bool NT, bool DAMP = false>
+// (the checked DAMP step with two rows needs 8 VGPRs more than the 128 of four waves per SIMD: it alone builds for fewer
+// waves instead of spilling; every other instantiation keeps its cap)
+__global__ __launch_bounds__(64 * kWavesRq)
+    __attribute__((amdgpu_waves_per_eu((R <= 2 && !(DAMP && CHECK && R == 2)) ? 4 : 2))) void k_leapfrog_rq(
     const LfParams p) {
   const int lane = static_cast<int>(threadIdx.x) & 63;
   const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);  // wave-uniform: tile math stays scalar
@@ -392,6 +415,21 @@ __global__ __launch_bounds__(64 * kWavesRq) __attribute__((amdgpu_waves_per_eu(R
     }
     sx = p.s[p.gx0 + xs];
   }
+  // sponge layers (DAMP): gx / rx of the plane one plane ahead like sx; per row gy, ry, per lane the two nodes' gz, rz
+  double gx = DAMP ? p.sp.gx[p.gx0 + xs] : 0.0, rx = DAMP ? p.sp.rx[p.gx0 + xs] : 1.0;
+  double gz0 = 0.0, gz1 = 0.0, rz0 = 1.0, rz1 = 1.0;
+  double gy[R], ry[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    gy[r] = DAMP && r < nre ? p.sp.gy[p.gy0 + yt + r] : 0.0;
+    ry[r] = DAMP && r < nre ? p.sp.ry[p.gy0 + yt + r] : 1.0;
+  }
+  if (DAMP && act) {
+    gz0 = p.sp.gz[p.gz0 + o0 - 1 - p.zs];
+    gz1 = p.sp.gz[p.gz0 + o0 - p.zs];
+    rz0 = p.sp.rz[p.gz0 + o0 - 1 - p.zs];
+    rz1 = p.sp.rz[p.gz0 + o0 - p.zs];
+  }
 
   for (i64 x = xs; x < xe; ++x, px += plane) {
     const bool more = x + 1 < xe;
@@ -399,6 +437,7 @@ __global__ __launch_bounds__(64 * kWavesRq) __attribute__((amdgpu_waves_per_eu(R
     double nhz[R];
     v2d nht = z2, nhb = z2;
     const double nsx = CHECK && more ? p.s[p.gx0 + x + 1] : 0.0;
+    const double ngx = DAMP && more ? p.sp.gx[p.gx0 + x + 1] : 0.0, nrx = DAMP && more ? p.sp.rx[p.gx0 + x + 1] : 1.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       nq[r] = z2;
@@ -431,6 +470,11 @@ __global__ __launch_bounds__(64 * kWavesRq) __attribute__((amdgpu_waves_per_eu(R
         v2d v;
         v.x = leapfrog(c[r].x, o[r].x, l0, tau2);
         v.y = leapfrog(c[r].y, o[r].y, l1, tau2);
+        if (DAMP) {
+          const double gxy = fmax(gx, gy[r]), rxy = fmin(rx, ry[r]);
+          v.x = leapfrog_damped(v.x, o[r].x, fmax(gxy, gz0), fmin(rxy, rz0));
+          v.y = leapfrog_damped(v.y, o[r].y, fmax(gxy, gz1), fmin(rxy, rz1));
+        }
         double* dst = out + px + base + r * pitch;
         if (ok0 && ok1)
           st2<NT>(dst, v);
@@ -464,6 +508,8 @@ __global__ __launch_bounds__(64 * kWavesRq) __attribute__((amdgpu_waves_per_eu(R
     ht = nht;
     hb = nhb;
     sx = nsx;
+    gx = ngx;
+    rx = nrx;
   }
   if (CHECK) {
     wave_reduce(emax, esum);
@@ -472,7 +518,7 @@ __global__ __launch_bounds__(64 * kWavesRq) __attribute__((amdgpu_waves_per_eu(R
 }
 
 template <int R>
-void launch_rq(const LfParams& p, int nblocks, bool check, bool nt, hipStream_t st);
+void launch_rq(const LfParams& p, int nblocks, bool check, bool nt, bool damp, hipStream_t st);
 
 // Host-side tiling plan shared by leapfrog_blocks() and launch_leapfrog().
 struct Plan {
@@ -548,9 +594,21 @@ Plan make_plan(const Layout& l, const LBox* boxes, int nbox, const LeapfrogTilin
 }
 
 template <int TY>
-void launch_lf_ty(const LfParams& p, int nblocks, bool check, bool nt, hipStream_t st) {
+void launch_lf_ty(const LfParams& p, int nblocks, bool check, bool nt, bool damp, hipStream_t st) {
   const dim3 block(kLanes, TY), grid(nblocks);
-  if (check) {
+  if (damp) {  // (sponge layers: the DAMP instantiations; the others are what they were)
+    if (check) {
+      if (nt)
+        hipLaunchKernelGGL((k_leapfrog_lds<TY, true, true, true>), grid, block, 0, st, p);
+      else
+        hipLaunchKernelGGL((k_leapfrog_lds<TY, true, false, true>), grid, block, 0, st, p);
+    } else {
+      if (nt)
+        hipLaunchKernelGGL((k_leapfrog_lds<TY, false, true, true>), grid, block, 0, st, p);
+      else
+        hipLaunchKernelGGL((k_leapfrog_lds<TY, false, false, true>), grid, block, 0, st, p);
+    }
+  } else if (check) {
     if (nt)
       hipLaunchKernelGGL((k_leapfrog_lds<TY, true, true>), grid, block, 0, st, p);
     else
@@ -564,9 +622,21 @@ void launch_lf_ty(const LfParams& p, int nblocks, bool check, bool nt, hipStream
 }
 
 template <int R>
-void launch_rq(const LfParams& p, int nblocks, bool check, bool nt, hipStream_t st) {
+void launch_rq(const LfParams& p, int nblocks, bool check, bool nt, bool damp, hipStream_t st) {
   const dim3 block(64 * kWavesRq), grid(nblocks);
-  if (check) {
+  if (damp) {
+    if (check) {
+      if (nt)
+        hipLaunchKernelGGL((k_leapfrog_rq<R, true, true, true>), grid, block, 0, st, p);
+      else
+        hipLaunchKernelGGL((k_leapfrog_rq<R, true, false, true>), grid, block, 0, st, p);
+    } else {
+      if (nt)
+        hipLaunchKernelGGL((k_leapfrog_rq<R, false, true, true>), grid, block, 0, st, p);
+      else
+        hipLaunchKernelGGL((k_leapfrog_rq<R, false, false, true>), grid, block, 0, st, p);
+    }
+  } else if (check) {
     if (nt)
       hipLaunchKernelGGL((k_leapfrog_rq<R, true, true>), grid, block, 0, st, p);
     else
@@ -714,7 +784,8 @@ int leapfrog_blocks(const Layout& l, const LBox* boxes, int nbox, const Leapfrog
 }
 
 void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox* boxes, int nbox,
-                     const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream) {
+                     const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream,
+                     const SpongeView* sponge) {
   Plan pl = make_plan(l, boxes, nbox, t);
   if (pl.nblocks == 0) return;
   LfParams& p = pl.prm;
@@ -729,19 +800,20 @@ void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double
   p.ry = c.ry;
   p.rz = c.rz;
   p.ct = ct;
-  const bool check = partials != nullptr;
+  const bool check = partials != nullptr, damp = sponge != nullptr;
+  if (damp) p.sp = *sponge;
   if (t.variant == 1) {
     switch (t.rows) {
-      case 1: launch_rq<1>(p, pl.nblocks, check, t.nt_store, stream); break;
-      case 2: launch_rq<2>(p, pl.nblocks, check, t.nt_store, stream); break;
-      case 4: launch_rq<4>(p, pl.nblocks, check, t.nt_store, stream); break;
-      default: launch_rq<8>(p, pl.nblocks, check, t.nt_store, stream); break;
+      case 1: launch_rq<1>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
+      case 2: launch_rq<2>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
+      case 4: launch_rq<4>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
+      default: launch_rq<8>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
     }
   } else {
     switch (t.ty) {
-      case 4: launch_lf_ty<4>(p, pl.nblocks, check, t.nt_store, stream); break;
-      case 8: launch_lf_ty<8>(p, pl.nblocks, check, t.nt_store, stream); break;
-      default: launch_lf_ty<16>(p, pl.nblocks, check, t.nt_store, stream); break;
+      case 4: launch_lf_ty<4>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
+      case 8: launch_lf_ty<8>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
+      default: launch_lf_ty<16>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
     }
   }
   W3D_HIP_CHECK(hipGetLastError());

@@ -28,6 +28,9 @@ void write_dump(const std::string& prefix, const Problem& p, const Layout& l, co
     << ", \"L\": " << p.L;
   // (a rectangular box: its three edges under a key of their own; a cube's sidecar is what it always was)
   if (p.is_box()) j << ", \"box\": [" << p.L << ", " << p.edge_y() << ", " << p.edge_z() << "]";
+  // (sponge layers: width, sigma as given (0: the default), face mask; absent without a sponge)
+  if (p.sponge.on())
+    j << ", \"sponge\": [" << p.sponge.width << ", " << p.sponge.sigma << ", " << p.sponge.faces << "]";
   j << ", \"tau\": " << p.tau << ", \"step\": " << step << ", \"t\": " << step * p.tau
     << ", \"shape\": [" << l.nx << ", " << l.ny << ", " << l.nz << "], \"offset\": [" << l.gx0 << ", " << l.gy0
     << ", " << l.gz0 << "], \"global_shape\": [" << p.N + 1 << ", " << p.N + 1 << ", " << p.N + 1

@@ -376,6 +376,15 @@ Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool 
     // (the stored u^{n+S−1} ghost planes: one plane per face)
     t.field_bytes += static_cast<double>((u.ghost_bits & 1) + (u.ghost_bits >> 1)) * plane_bytes;
     for (const MsgPlan& m : u.msgs) t.halo_bytes += static_cast<double>(m.count) * sizeof(double);
+    // sponge layers: a fused unit's slabs are recomputed from its inputs (k_sponge_box) — two levels read on every box
+    // grown by the unit's steps and clipped to the interior, two levels written on the box
+    if (s.prob.sponge.on() && u.fused())
+      for (const LBox& b : sponge_boxes(s.prob, l, u.steps)) {
+        const double g = static_cast<double>(imin(b.x1 + u.steps, l.cx1) - imax(b.x0 - u.steps, l.cx0)) *
+                         static_cast<double>(imin(b.y1 + u.steps, l.cy1) - imax(b.y0 - u.steps, l.cy0)) *
+                         static_cast<double>(imin(b.z1 + u.steps, l.cz1) - imax(b.z0 - u.steps, l.cz0));
+        t.field_bytes += 2.0 * (g + static_cast<double>(b.count())) * sizeof(double);
+      }
   }
   if (s.push) {  // each pass but the last forwards T planes of u^{n+S} and T − 1 of u^{n+S−1} per face
     const double T = static_cast<double>(l.xg);

@@ -38,6 +38,17 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
   if (const char* v = std::getenv("W3D_TB_MINCHUNK")) o.tiling_tb.min_chunk = std::atoi(v);
   if (const char* v = std::getenv("W3D_TB_XCDBLOCKS")) o.tiling_tb.xcd_blocks = *v == '1';
   if (const char* v = std::getenv("W3D_TB_XCDREMAP")) o.tiling_tb.xcd_remap = *v == '1';  // (A/B runs)
+  if (prob.sponge.on()) {  // (sponge layers: solver.hpp sponge())
+    W3D_REQUIRE(!o.fake_comm, "sponge: not on a fake rank");
+    W3D_REQUIRE(!o.push && !o.sdma, "sponge: not on the push or copy-engine transports");
+    W3D_REQUIRE(world == 1 && !loopback_, "sponge: one GPU rank only (no GpuGroup, RCCL ranks, --np or runtime=\"process\": the "
+                                          "layers' slabs are recomputed over the whole domain)");
+    // (k_leapfrog_rq<8> spills with or without DAMP, the damped one 340-404 B per lane: profiles/sponge/README.md)
+    W3D_REQUIRE(!(o.tiling.variant == 1 && o.tiling.rows == 8),
+                "sponge: the register-queue single step with 8 rows per wave spills its damped form; use 1, 2 or 4 rows");
+    W3D_REQUIRE(o.temporal < 2 || o.tb,
+                "sponge: tb = false runs k_leapfrog2 pairs, which have no damped form; use the LDS passes or temporal = 1");
+  }
   // (the push transport's kernels exist for cubes only: kernels_leapfrog_tb_push.hip)
   W3D_REQUIRE(!(o.push && world > 1 && coef_.box),
               "the push transport has no rectangular-box kernels: run a --box problem over rccl or sdma");
@@ -149,6 +160,42 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
   ct_.resize(static_cast<size_t>(sch_.prob.K + 1));
   for (int n = 0; n <= sch_.prob.K; ++n) ct_[static_cast<size_t>(n)] = time_factor(sch_.prob, n);
   if (loopback_) sch_.opt.graph = false;  // (group ranks: the GpuGroup captures the whole group solve itself)
+  if (sch_.prob.sponge.on()) {
+    const SpongeTables t = sponge_tables(sch_.prob);
+    const size_t n = static_cast<size_t>(sch_.prob.N + 3);
+    W3D_HIP(hipMalloc(&sponge_dev_, 6 * n * sizeof(double)));
+    for (int a = 0; a < 3; ++a) {
+      W3D_HIP(hipMemcpy(sponge_dev_ + a * n, t.g[a].data(), n * sizeof(double), hipMemcpyHostToDevice));
+      W3D_HIP(hipMemcpy(sponge_dev_ + (3 + a) * n, t.r[a].data(), n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    sponge_view_ = SpongeView{sponge_dev_ + 1,         sponge_dev_ + n + 1,     sponge_dev_ + 2 * n + 1,
+                              sponge_dev_ + 3 * n + 1, sponge_dev_ + 4 * n + 1, sponge_dev_ + 5 * n + 1};
+    sponge_box_prepare();  // (the dynamic-LDS limit: before any capture)
+    for (int st = 2; st <= 5; ++st) sponge_boxes_[st] = sponge_boxes(sch_.prob, sch_.lay, st);
+  }
+}
+
+void GpuSolver::sponge_check_nodes(const i64* ijk, int n, const char* what) const {
+  if (!sponge()) return;
+  const Sponge& sp = sch_.prob.sponge;
+  const i64 reach = static_cast<i64>(sp.width) + sch_.opt.temporal;
+  for (int q = 0; q < n; ++q)
+    for (int a = 0; a < 3; ++a)
+      for (int side = 0; side < 2; ++side) {
+        if (!((sp.faces >> (2 * a + side)) & 1)) continue;
+        const i64 d = side == 0 ? ijk[3 * q + a] : sch_.prob.N - ijk[3 * q + a];
+        W3D_REQUIRE(d > reach, std::string("sponge: ") + what + " " + std::to_string(q) + " lies " + std::to_string(d) +
+                                   " nodes from a damped face, within width + temporal = " + std::to_string(reach) +
+                                   " (the cone kernels recompute with the undamped operator)");
+      }
+}
+
+void GpuSolver::sponge_unit(const UnitPlan& u) {
+  if (!sponge() || !u.fused()) return;
+  timed(kPhaseCompute, s0_, [&] {
+    for (const LBox& b : sponge_boxes_[u.steps])
+      launch_sponge_box(sch_.lay, coef_, sponge_view_, u_[old_], u_[cur_], u_[uf_[0]], u_[uf_[1]], b, u.steps, s0_);
+  });
 }
 
 GpuSolver::~GpuSolver() {
@@ -170,7 +217,7 @@ GpuSolver::~GpuSolver() {
   for (BoxCopyTable& t : pack_tab_) free_box_copy_table(t);
   for (BoxCopyTable& t : unpack_tab_) free_box_copy_table(t);
   if (pk_dev_) (void)hipFree(pk_dev_);
-  for (double* p : {u_[0], u_[1], u_[2], u_[3], d_s_, send_buf_, recv_buf_, init_[0], init_[1]})
+  for (double* p : {u_[0], u_[1], u_[2], u_[3], d_s_, send_buf_, recv_buf_, init_[0], init_[1], sponge_dev_})
     if (p) (void)hipFree(p);
   if (energy_part_) (void)hipFree(energy_part_);
   if (recv_dev_) (void)hipFree(recv_dev_);
@@ -202,7 +249,7 @@ GpuSolver::~GpuSolver() {
 size_t GpuSolver::device_bytes() const {
   return static_cast<size_t>(sch_.nbuf) * static_cast<size_t>(sch_.lay.bytes()) +
          recv_bytes_ + send_bytes_ + static_cast<size_t>(n_partials_) * sizeof(Partial) +
-         static_cast<size_t>(sch_.prob.N + 3) * sizeof(double) + tb_bytes_ +
+         static_cast<size_t>(sch_.prob.N + 3) * sizeof(double) * (sponge() ? 7u : 1u) + tb_bytes_ +
          ((init_[0] ? 1u : 0u) + (init_[1] ? 1u : 0u)) * static_cast<size_t>(init_lay_.bytes()) +
          (energy_part_ ? static_cast<size_t>(energy_partials(sch_.lay) + 2) * sizeof(Partial) : 0u) +
          recv_.size() * (sizeof(Receiver) + static_cast<size_t>(sch_.prob.K + 1) * sizeof(double)) +
@@ -262,6 +309,7 @@ void GpuSolver::set_receivers(const i64* ijk, int R) {
   }
   std::vector<std::array<i64, 3>> nodes(static_cast<size_t>(R));
   for (int r = 0; r < R; ++r) nodes[static_cast<size_t>(r)] = {ijk[3 * r], ijk[3 * r + 1], ijk[3 * r + 2]};
+  sponge_check_nodes(ijk, R, "receiver");
   std::vector<Receiver> mine = plan_receivers(sch_.prob, sch_.dims, sch_.rank, sch_.lay, nodes);  // (refuses bad nodes)
   DeviceScope scope(dev_, true);
   drop_graphs();
@@ -317,6 +365,7 @@ void GpuSolver::set_sources(const i64* ijk, int Q, const double* w) {
                                 "wavelet from)");
   }
   const std::vector<double> a = source_addends(sch_.prob, ijk, Q, w);  // (refuses bad nodes and samples)
+  sponge_check_nodes(ijk, Q, "source");
   std::vector<std::array<i64, 3>> nodes(static_cast<size_t>(Q));
   for (int q = 0; q < Q; ++q) nodes[static_cast<size_t>(q)] = {ijk[3 * q], ijk[3 * q + 1], ijk[3 * q + 2]};
   // (radius: the largest ball any pass needs, so one plan and one set of colour classes serves every unit)
@@ -434,8 +483,9 @@ void GpuSolver::phase_init() {
     W3D_HIP(hipMemsetAsync(trace_, 0xFF, static_cast<size_t>(K + 1) * recv_.size() * sizeof(double), s0_));
   // one rank on the LDS kernel: the first pass starts from the analytic u⁰, u¹ itself (no init kernel, no reads)
   analytic_ = (sch_.mode == Mode::kFusedSingle || sch_.mode == Mode::kDeepTb) && sch_.analytic_ok() && resume_n_ == 0 &&
-              !initial_ && !recording_ && n_src_ == 0;  // (receivers: both start levels are stored, rows 0 and 1 are
-                                                        // gathered; sources: u¹ is corrected in memory)
+              !initial_ && !recording_ && n_src_ == 0 && !sponge();  // (receivers: both start levels are stored, rows 0
+                                                        // and 1 are gathered; sources: u¹ is corrected in memory;
+                                                        // sponge layers: the start is stored, as with receivers)
   if (resume_n_ > 0) {  // loaded state: u^{n0−1} → buf 0, u^{n0} → buf 1 (ghosts included)
     const size_t bytes = static_cast<size_t>(sch_.lay.bytes());
     timed(kPhaseInit, s0_, [&] {
@@ -458,7 +508,7 @@ void GpuSolver::phase_init() {
     start_n_ = 1;
   } else if (analytic_) {
     start_n_ = 1;
-  } else if (sch_.opt.init2 && K >= 2 && !recording_ && n_src_ == 0) {
+  } else if (sch_.opt.init2 && K >= 2 && !recording_ && n_src_ == 0 && !sponge()) {
     // u¹ -> buf 0, u² -> buf 1 analytically (no read pass), ghosts included; the first leapfrog step is n = 2
     timed(kPhaseInit, s0_, [&] {
       launch_init_two(sch_.lay, coef_, s, u_[0], u_[1], ct_[2], is_check_[2] ? partials_ : nullptr, s0_);
@@ -483,7 +533,8 @@ void GpuSolver::phase_init() {
   }
   cur_ = 1;
   old_ = 0;
-  units_ = plan_units(sch_, start_n_, analytic_, n_src_ > 0);
+  // (sponge layers: like sources, the last pass keeps both levels — a rebuild would need the slabs' recomputation too)
+  units_ = plan_units(sch_, start_n_, analytic_, n_src_ > 0 || sponge());
   if (sch_.push) push_upload();
 }
 
@@ -547,7 +598,7 @@ void GpuSolver::unit_shell(int i) {
   } else if (sch_.mode == Mode::kSingleStep && sch_.split()) {
     timed(kPhaseShell, s0_, [&] {
       launch_leapfrog(sch_.lay, coef_, u_[cur_], u_[old_], sch_.shell.data(), static_cast<int>(sch_.shell.size()), d_s_ + 1,
-                      ct_[static_cast<size_t>(nc)], chk ? partials_ : nullptr, sch_.opt.tiling, s0_);
+                      ct_[static_cast<size_t>(nc)], chk ? partials_ : nullptr, sch_.opt.tiling, s0_, sponge_arg());
     });
   }
   if (u.exchange) capture::record(ev_shell_, s0_);
@@ -721,6 +772,7 @@ void GpuSolver::unit_interior(int i) {
     if (sch_.mode != Mode::kDeepTb) tb_slots_ = 0;
     const LBox& b = u.interior;
     if (!b.empty()) tb_pass(u, b, kPhaseCompute);
+    sponge_unit(u);  // (sponge layers: the slabs of both outputs again, damped, from the unit's inputs)
     // (the shells ran on the side stream: join it before the reductions read their partials)
     if (wait) {
       capture::wait(s0_, ev_halo_);
@@ -741,19 +793,19 @@ void GpuSolver::unit_interior(int i) {
                          chk ? partials_ : nullptr, sch_.opt.tiling2, s0_);
       else
         launch_leapfrog(sch_.lay, coef_, u_[cur_], u_[old_], &sch_.full, 1, s, ct, chk ? partials_ : nullptr, sch_.opt.tiling,
-                        s0_);
+                        s0_, sponge_arg());
     });
     np = u.fused() ? n_fused_ : n_full_;
   } else if (sch_.split()) {
     timed(kPhaseCompute, s0_, [&] {
       launch_leapfrog(sch_.lay, coef_, u_[cur_], u_[old_], &sch_.interior, 1, s, ct, chk ? partials_ + n_shell_ : nullptr,
-                      sch_.opt.tiling, s0_);
+                      sch_.opt.tiling, s0_, sponge_arg());
     });
     np = n_shell_ + n_int_;
   } else {
     timed(kPhaseCompute, s0_, [&] {
       launch_leapfrog(sch_.lay, coef_, u_[cur_], u_[old_], &sch_.full, 1, s, ct, chk ? partials_ : nullptr, sch_.opt.tiling,
-                      s0_);
+                      s0_, sponge_arg());
     });
     np = n_full_;
   }

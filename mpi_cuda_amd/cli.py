@@ -62,6 +62,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="point sources w(t) delta(x - x_s): FILE lists one source per line as i j k f0 t0 amp (a node "
                          "strictly inside the grid and a Ricker wavelet of peak frequency f0 centred at t0); the error "
                          "lines then have no meaning (backends hip and cpu; not with --resume)")
+    ap.add_argument("--sponge", default="", metavar="W[,SIGMA[,FACES]]",
+                    help="absorbing sponge layers of W nodes next to the faces FACES, a subset of the letters xXyYzZ (lower "
+                         "case: the low face; default all six), peak damping rate SIGMA (default 3 ln(1000) / (2 W h)); "
+                         "one rank, backends hip and cpu; the error lines then have no meaning")
     ap.add_argument("--force", action="store_true", help="run even if the CFL condition is violated")
     ap.add_argument("--quiet", action="store_true")
     return ap
@@ -91,6 +95,20 @@ def main(argv=None) -> int:
         ap.error("--sources and --resume exclude each other")
     if bool(a.receivers) != bool(a.traces):
         ap.error("--receivers FILE and --traces OUT go together")
+    sponge = None
+    if a.sponge:
+        part = a.sponge.split(",")
+        try:
+            if not 1 <= len(part) <= 3:
+                raise ValueError(a.sponge)
+            if len(part) == 3 and not part[2]:
+                ap.error("--sponge: FACES is empty (leave the last comma out for all six faces)")
+            sponge = (int(part[0]), float(part[1]) if len(part) > 1 and part[1] else 0.0,
+                      part[2] if len(part) > 2 else 63)
+        except ValueError:
+            ap.error("--sponge expects W[,SIGMA[,FACES]]: an integer width and an optional number")
+        if isinstance(sponge[2], str) and any(ch not in "xXyYzZ" for ch in sponge[2]):
+            ap.error("--sponge: FACES is a subset of the letters xXyYzZ")
     import torch
     import torch.distributed as dist
 
@@ -101,7 +119,10 @@ def main(argv=None) -> int:
     from .utils.report import gcell_per_s
 
     spec = ProblemSpec(N=a.N, tau=a.tau, K=a.K, L=a.L, check_every=a.check_every,
-                       Ly=box[1] if box else None, Lz=box[2] if box else None)
+                       Ly=box[1] if box else None, Lz=box[2] if box else None, sponge=sponge)
+    if spec.sponge is not None:
+        print("wave3d: sponge layers are set: the error columns compare with the undamped eigenmode and have no meaning",
+              file=sys.stderr)
     box_note = " box=" + ",".join(f"{e:g}" for e in spec.edges) if spec.is_box else ""
     if not spec.cfl_ok:
         form = "tau*sqrt(1/hx^2+1/hy^2+1/hz^2)" if spec.is_box else "tau*sqrt(3)/h"
@@ -209,20 +230,23 @@ def main(argv=None) -> int:
                            "gcell_per_s": gcell_per_s(a.N, a.K, best),
                            **({"energy_start": e_start, "energy_end": e_end} if a.energy else {}),
                            **({"sources": n_sources} if a.sources else {}),
+                           **({"sponge": list(spec.sponge)} if spec.sponge is not None else {}),
                            "steps": [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]}, f)
     if a.traces:
         dumpio.save_traces(a.traces, s.traces().numpy(), nodes, N=a.N, K=a.K, L=a.L, tau=a.tau, box=spec.edges)
     if a.dump or a.checkpoint:
+        sponge_meta = {"sponge": list(spec.sponge)} if spec.sponge is not None else None  # (absent without a sponge)
+
         def write(prefix, which):
             if s.transport in ("loopback", "rccl-self", "push", "sdma"):
                 if rank == 0:
                     dumpio.save(prefix, s.global_field(which).numpy(), N=a.N, L=a.L, tau=a.tau,
-                                step=a.K - which, box=spec.edges)
+                                step=a.K - which, box=spec.edges, extra=sponge_meta)
                 return
             f = s.owned_field(which)
             off = s.native.plan.box[0::2] if s.transport == "torch" else (0, 0, 0)
             dumpio.save(prefix, f.numpy(), N=a.N, L=a.L, tau=a.tau, step=a.K - which, offset=off, rank=rank,
-                        world=s.world, dims=s.dims, box=spec.edges)
+                        world=s.world, dims=s.dims, box=spec.edges, extra=sponge_meta)
 
         if a.dump:
             write(a.dump, 0)

@@ -46,7 +46,12 @@ class ProblemSpec:
     """N intervals per axis ((N+1)³ nodes), time step tau, K steps, cube edge L (positional CLI ``N tau K [L]``).
 
     ``Ly`` / ``Lz`` make the domain a rectangular box Lx × Ly × Lz with Lx = L (CLI ``--box LX,LY,LZ``); None means
-    "= L". A spec whose three edges are equal is a cube and evaluates exactly the cube's expressions."""
+    "= L". A spec whose three edges are equal is a cube and evaluates exactly the cube's expressions.
+
+    ``sponge = (width, sigma, faces)`` (or just ``width``, or ``(width, sigma)``) puts an absorbing layer of ``width``
+    nodes next to the faces of the mask ``faces`` (bits 0..5: x-, x+, y-, y+, z-, z+, or a string of the letters
+    ``xXyYzZ``, lower case = low face; default all six) with peak damping rate ``sigma`` (0: the default
+    3 ln(1000) / (2 width h)); CLI ``--sponge W[,SIGMA[,FACES]]``. None, width 0 or faces 0: no sponge."""
 
     N: int = 512
     tau: float = 1e-3
@@ -56,8 +61,33 @@ class ProblemSpec:
     extra: dict = field(default_factory=dict)
     Ly: float | None = None
     Lz: float | None = None
+    sponge: tuple | int | None = None
 
     def __post_init__(self) -> None:
+        if self.sponge is not None:
+            sp = self.sponge if isinstance(self.sponge, (tuple, list)) else (self.sponge,)
+            if not 1 <= len(sp) <= 3:
+                raise ValueError("sponge: (width, sigma, faces)")
+            width = int(sp[0])
+            sigma = 0.0 if len(sp) < 2 or sp[1] is None else float(sp[1])
+            faces = 63 if len(sp) < 3 or sp[2] is None else sp[2]
+            if isinstance(faces, str):
+                if not faces:
+                    raise ValueError("sponge: faces is empty (None selects all six)")
+                if any(ch not in "xXyYzZ" for ch in faces):
+                    raise ValueError("sponge: faces is a subset of the letters xXyYzZ")
+                faces = sum(1 << "xXyYzZ".index(ch) for ch in set(faces))
+            faces = int(faces)
+            if width < 0:
+                raise ValueError("sponge: the width must be >= 0")
+            if not (math.isfinite(sigma) and sigma >= 0.0):
+                raise ValueError("sponge: sigma must be finite and >= 0 (0 selects the default)")
+            if not 0 <= faces <= 63:
+                raise ValueError("sponge: faces is a mask of bits 0..5 (x-, x+, y-, y+, z-, z+)")
+            if width > 0 and faces and 2 * width > self.N - 1:
+                raise ValueError(f"sponge: two layers of width {width} do not fit into the {self.N - 1} interior nodes "
+                                 "of an axis (2 * width <= N - 1)")
+            self.sponge = (width, sigma, faces) if width > 0 and faces else None
         if self.N < 2:
             raise ValueError("N must be >= 2")
         if not (self.tau > 0 and math.isfinite(self.tau)):
@@ -142,10 +172,12 @@ class ProblemSpec:
     def native(self):
         from .._native import load
 
+        C = load()
+        kw = {} if self.sponge is None else {"sponge": C.Sponge(*self.sponge)}
         if self.Ly is None and self.Lz is None:
-            return load().Problem(self.N, self.tau, self.K, self.L)
+            return C.Problem(self.N, self.tau, self.K, self.L, **kw)
         _, ly, lz = self.edges
-        return load().Problem(self.N, self.tau, self.K, self.L, Ly=ly, Lz=lz)
+        return C.Problem(self.N, self.tau, self.K, self.L, Ly=ly, Lz=lz, **kw)
 
     def as_dict(self) -> dict:
         d = asdict(self)
@@ -155,6 +187,10 @@ class ProblemSpec:
             d.pop("Lz")
         else:
             d["Ly"], d["Lz"] = self.edges[1], self.edges[2]
+        if self.sponge is None:  # (... and so is a spec's without a sponge)
+            d.pop("sponge")
+        else:
+            d["sponge"] = list(self.sponge)
         return d
 
 

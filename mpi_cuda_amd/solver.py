@@ -100,8 +100,14 @@ class Solver:
                  tb_min_planes: int | None = None, rccl: bool = True, autotune: bool = False,
                  autotune_rounds: int = 5, copy_engines: bool = False, fused_pack: bool = True,
                  ghost_store: bool = True, keep_prev: bool = False,
-                 runtime: str = "inproc"):
+                 runtime: str = "inproc", sponge=None):
+        import dataclasses
+
         import torch.distributed as dist
+
+        # sponge = (width, sigma, faces): absorbing layers (ProblemSpec.sponge; given here it replaces the spec's)
+        if sponge is not None:
+            spec = dataclasses.replace(spec, sponge=sponge)
 
         if not spec.cfl_ok and not force:
             raise ValueError(f"CFL violated: courant = {spec.courant:.4f} > 1 (tau_max = {spec.tau_max:.3e}); "
@@ -114,6 +120,19 @@ class Solver:
         self.spec, self.rank, self.world = spec, rank, world
         self.backend, self.transport = _resolve(backend, transport, world)
         self.decomp = decomp
+        if spec.sponge is not None:
+            # one native rank: CpuSolver is the definition, GpuSolver matches it; nothing else has a damped step
+            if runtime == "process":
+                raise ValueError("sponge: not with runtime='process' (one in-process rank only)")
+            if world > 1:
+                raise ValueError("sponge: one rank only (a world larger than 1 of any kind is not supported)")
+            if self.backend == "torch" or self.transport == "torch":
+                raise ValueError("sponge: the native backends only (backend 'hip' with transport 'rccl', or 'cpu')")
+            if self.transport in ("push", "push-ipc", "sdma", "sdma-ipc") or copy_engines:
+                raise ValueError("sponge: not on the push or copy-engine transports")
+            if not tb and temporal >= 2:
+                raise ValueError("sponge: tb=False runs k_leapfrog2 pairs, which have no damped form; use the LDS "
+                                 "passes or temporal=1")
         self._impl = None
         self._initial = None  # (set_initial's global phi, psi: a group's E(1/2) is computed from them on the host)
         if runtime not in ("inproc", "process"):

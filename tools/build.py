@@ -52,6 +52,7 @@ LIB_SOURCES = [
     ("src/kernels_initial.hip", "hip"),
     ("src/kernels_record.hip", "hip"),
     ("src/kernels_source.hip", "hip"),
+    ("src/kernels_sponge.hip", "hip"),
     ("src/kernels_leapfrog_tb.hip", "hip"),
     ("src/kernels_leapfrog_tb_push.hip", "hip"),
     ("src/kernels_leapfrog_p2.hip", "hip"),

@@ -670,7 +670,9 @@ __global__ __launch_bounds__(256) void k_error(const ErrParams p) {
     const i64 y = p.y0 + q / p.nz, z = p.z0 + q % p.nz;
     const double v = p.u[(x + 1) * p.plane + (y + 1) * p.pitch + (z + 1 + p.zs)];
     const double e = fabs(v - analytic_row(p.s[p.gx0 + x], p.s[p.gy0 + y], p.ct) * p.s[p.gz0 + z]);
-    emax = e;
+    // (not emax = e: a NaN here would stay in its lane through wave_reduce and swallow every partner maximum routed
+    // through it; the maximum skips NaN nodes, the sum carries them — docs/ARCHITECTURE.md "Non-finite fields")
+    emax = e > emax ? e : emax;
     esum = err_sq_acc(e, 0.0);
   }
   wave_reduce(emax, esum);

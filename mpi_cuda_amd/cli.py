@@ -227,6 +227,7 @@ def main(argv=None) -> int:
             with open(a.json, "w") as f:
                 json.dump({"backend": s.backend, "transport": s.transport, "N": a.N, "tau": a.tau, "K": a.K, "L": a.L,
                            **({"box": list(spec.edges)} if spec.is_box else {}), "ranks": s.world, "dims": list(s.dims), "solve_s": best,
+                           "finite": bool(r.finite),
                            "gcell_per_s": gcell_per_s(a.N, a.K, best),
                            **({"energy_start": e_start, "energy_end": e_end} if a.energy else {}),
                            **({"sources": n_sources} if a.sources else {}),

@@ -63,6 +63,7 @@ struct Args {
   int target_blocks = 0;
   int nt_store = -1;
   std::string json, dump, trace, checkpoint, resume;
+  std::string speed;    // --speed PREFIX: the wave speed c(x) from the dump PREFIX.c (the --initial format)
   std::string initial;  // --initial PREFIX: solve from PREFIX.phi (u(.,0)) and, if present, PREFIX.psi (u_t(.,0))
   std::string receivers;  // --receivers FILE: record u^n at the listed grid nodes ("i j k" per line), n = 0..K
   std::string sources;    // --sources FILE: point sources ("i j k f0 t0 amp" per line, a Ricker wavelet each)
@@ -97,6 +98,9 @@ std::string box_json(const Problem& p);
 std::string sponge_json(const Problem& p);
 // --sponge: says once on stderr that the error columns have no meaning (nothing without a sponge)
 void sponge_notice(const Problem& p);
+// --speed: ", \"speed\": [min c, max c]" for the JSON summaries (empty without a speed field), and the notice on stderr
+std::string speed_json(bool on, const SpeedRange& r);
+void speed_notice(bool on);
 // --energy: the line printed after the error log, and the two keys it adds to --json
 void print_energy(double e_start, double e_end);
 std::string energy_json(double e_start, double e_end);

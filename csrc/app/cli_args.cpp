@@ -119,6 +119,10 @@ constexpr Personality kPersonalities[] = {
                "  --sponge W[,SIGMA[,FACES]]  absorbing sponge layers of W nodes next to the faces FACES, a subset of the\n"
                "                     letters xXyYzZ (lower case: the low face; default all six), peak damping rate SIGMA\n"
                "                     (default 3 ln(1000) / (2 W h)). One GPU rank or --cpu. The error lines then have no meaning\n"
+               "  --speed P          variable wave speed: solve u_tt = c(x)^2 Lap u with c from the dump P.c (the --initial\n"
+               "                     format; face values ignored, interior values finite and > 0; courant * max c <= 1 unless\n"
+               "                     --force). One GPU rank (single steps and two-step pairs; --temporal 1 or 2) or --cpu;\n"
+               "                     not with --resume. The error lines then have no meaning\n"
                "  --force            run even if the CFL condition is violated\n"
                "  --quiet            only the summary\n");
   std::exit(2);
@@ -207,6 +211,7 @@ Args parse(int argc, char** argv) {
     else if (s == "--checkpoint") a.checkpoint = next();
     else if (s == "--resume") a.resume = next();
     else if (s == "--initial") a.initial = next();
+    else if (s == "--speed") a.speed = next();
     else if (s == "--receivers") a.receivers = next();
     else if (s == "--traces") a.traces = next();
     else if (s == "--sources") a.sources = next();
@@ -307,6 +312,9 @@ Args parse(int argc, char** argv) {
   if (!a.sources.empty() && (a.serve || a.fake_rank >= 0)) usage("--sources: not with --serve or --fake-rank");
   if (a.prob.sponge.on() && (a.np > 1 || a.group > 0 || a.serve || a.fake_rank >= 0))
     usage("sponge: one rank only (not with --np, --group, --serve or --fake-rank)");
+  if (!a.speed.empty() && (a.np > 1 || a.group > 0 || a.serve || a.fake_rank >= 0))
+    usage("speed: one rank only (not with --np, --group, --serve or --fake-rank)");
+  if (!a.speed.empty() && !a.resume.empty()) usage("speed: not together with --resume");
   if (a.repeat < 1) a.repeat = 1;
   return a;
 }
@@ -351,6 +359,15 @@ void sponge_notice(const Problem& p) {
   if (p.sponge.on())
     std::fprintf(stderr, "wave3d: sponge layers are set: the error columns compare with the undamped eigenmode and have "
                          "no meaning\n");
+}
+std::string speed_json(bool on, const SpeedRange& r) {
+  if (!on) return "";
+  return ", \"speed\": [" + jexact(r.cmin) + ", " + jexact(r.cmax) + "]";
+}
+void speed_notice(bool on) {
+  if (on)
+    std::fprintf(stderr, "wave3d: a speed field is set: the error columns compare with the constant-speed eigenmode and "
+                         "have no meaning\n");
 }
 void print_energy(double e_start, double e_end) {
   std::printf("Energy: E(1/2) = %.15e, E(K-1/2) = %.15e, drift = %.3e\n", e_start, e_end,

@@ -23,6 +23,13 @@ int run_cpu(const Args& a) {
     load_initial(a.initial, a.prob, phi, psi);
     s.set_initial(phi.data(), psi.empty() ? nullptr : psi.data());
   }
+  if (!a.speed.empty()) {
+    std::vector<double> c;
+    load_speed(a.speed, a.prob, c);
+    s.set_speed(c.data(), a.force);
+  }
+  const SpeedRange srange = s.speed_range();
+  const SpeedRange* sr = s.speed() ? &srange : nullptr;
   std::vector<i64> nodes;
   if (!a.receivers.empty()) {
     nodes = load_receivers(a.receivers);
@@ -47,7 +54,7 @@ int run_cpu(const Args& a) {
       if (cmd == "dump") {
         std::string prefix;
         in >> prefix;
-        write_dump(prefix, a.prob, s.layout(), s.field(0), 0, 1, Dims{1, 1, 1});
+        write_dump(prefix, a.prob, s.layout(), s.field(0), 0, 1, Dims{1, 1, 1}, -1, sr);
         return "{\"dump\": " + jstr(prefix) + "}";
       }
       return "{\"error\": " + jstr("unknown command: " + cmd) + "}";
@@ -91,9 +98,10 @@ int run_cpu(const Args& a) {
       << ", \"boundary\": " << jnum(rb.boundary_s) << ", \"exchange\": " << jnum(rb.exchange_s) << "}"
       << (a.energy ? energy_json(e_start, e_end) : std::string())
       << (a.sources.empty() ? std::string() : ", \"sources\": " + std::to_string(s.sources()))
+      << speed_json(s.speed(), srange)
       << ", \"steps\": " << steps_json(r.steps, r.max_err, r.rms_err) << "}\n";
   }
-  if (!a.dump.empty()) write_dump(a.dump, a.prob, s.layout(), s.field(0), 0, 1, Dims{1, 1, 1});
+  if (!a.dump.empty()) write_dump(a.dump, a.prob, s.layout(), s.field(0), 0, 1, Dims{1, 1, 1}, -1, sr);
   if (!a.traces.empty()) write_traces(a.traces, a.prob, nodes, s.traces());
   if (!a.checkpoint.empty())
     write_checkpoint(a.checkpoint, a.prob, s.layout(), s.field(0), s.field(1), 0, 1, Dims{1, 1, 1});
@@ -103,6 +111,7 @@ int run_cpu(const Args& a) {
 // One rank of the multi-process CPU path (--cpu --np P): the reference's MPI / MPI+OpenMP programs.
 int run_cpu_rank(const Args& a, ShmGroup& g, int rank) {
   W3D_REQUIRE(a.resume.empty(), "--resume runs on one CPU process (--cpu) or on the GPU path, not the CPU ranks");
+  W3D_REQUIRE(a.speed.empty(), "speed: the distributed CPU program has no coefficient field (one CPU process: --cpu)");
   W3D_REQUIRE(a.initial.empty(), "--initial runs on one CPU process (--cpu) or on the GPU path, not the CPU ranks");
   try {
     CpuRankSolver s(a.prob, g, rank, a.check_every, a.threads);

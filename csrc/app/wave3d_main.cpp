@@ -297,6 +297,13 @@ int run_gpu(const Args& a) {
     load_initial(a.initial, a.prob, phi, psi);
     s->set_initial(phi.data(), psi.empty() ? nullptr : psi.data());
   }
+  if (!a.speed.empty()) {
+    W3D_REQUIRE(world == 1 && !fake, "speed: one GPU rank that spans the domain only");
+    std::vector<double> c;
+    load_speed(a.speed, a.prob, c);
+    s->set_speed(c.data(), a.force);
+  }
+  const SpeedRange srange = s->speed_range();
   std::vector<i64> nodes;
   if (!a.receivers.empty()) {
     W3D_REQUIRE(world == 1, "--receivers / --traces: one rank only (gathering traces from several processes is not "
@@ -381,7 +388,8 @@ int run_gpu(const Args& a) {
   // --energy: of the last solve above, like --dump
   const double e_start = a.energy ? s->energy(1) : 0.0, e_end = a.energy ? s->energy(0) : 0.0;
   // --dump: u^K of the last solve above (before the traced solve below overwrites the fields with its own)
-  if (!a.dump.empty()) write_dump(a.dump, a.prob, s->layout(), s->download(0), rank, world, s->dims());
+  if (!a.dump.empty())
+    write_dump(a.dump, a.prob, s->layout(), s->download(0), rank, world, s->dims(), -1, s->speed() ? &srange : nullptr);
   if (!a.traces.empty()) write_traces(a.traces, a.prob, nodes, s->traces().values);  // (one rank: every slot, in order)
   // per-phase breakdown of the schedule that was timed: one more solve with the same kernels, traced with events
   PhaseTimes ph;
@@ -476,6 +484,7 @@ int run_gpu(const Args& a) {
           << "}";
       if (a.energy) j << energy_json(e_start, e_end);
       if (!a.sources.empty()) j << ", \"sources\": " << s->sources();
+      j << speed_json(s->speed(), srange);
       j << ", \"solve_times_s\": [";
       for (size_t i = 0; i < times.size(); ++i) j << (i ? ", " : "") << jnum(times[i]);
       j << "], \"steps\": [";
@@ -542,6 +551,9 @@ int main(int argc, char** argv) {
     W3D_REQUIRE(!a.prob.sponge.on() || (!group && lworld <= 1),
                 "sponge: one rank only (ranks of a multi-process world are not supported)");
     sponge_notice(a.prob);
+    W3D_REQUIRE(a.speed.empty() || (!group && lworld <= 1),
+                "speed: one rank only (ranks of a multi-process world are not supported)");
+    speed_notice(!a.speed.empty());
     W3D_REQUIRE(a.sources.empty() || (!group && lworld <= 1),
                 "sources: one rank only (ranks of a multi-process world are not supported)");
     W3D_REQUIRE(a.receivers.empty() || (!group && lworld <= 1),

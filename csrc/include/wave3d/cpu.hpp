@@ -110,6 +110,23 @@ inline Layout initial_layout(const Problem& p, const Layout& solve) {
 }
 void initial_to_local(const Layout& src, const double* global, double* local);
 
+// The eigenmode φ = (s_x·s_y)·s_z (stencil.hpp phi: cpu_init_first's u⁰) as a local array in `src` = initial_layout(...),
+// zeros outside the global grid: what a solve with a speed field and no set_initial starts from.
+std::vector<double> eigenmode_local(const Problem& p, const Layout& src);
+
+// Variable wave speed u_tt = c²(x)·Δu: c is a GLOBAL (N+1)³ C-order field, face values ignored. speed_to_local checks
+// every global interior value (finite and > 0, otherwise refused with "speed:"), returns their minimum and maximum, and
+// fills two local arrays in the layout `l`, ghost layers included: c2[p] = c·c and lamf[p] = Coeffs::lam·c2[p], one
+// rounding each, both exact zeros on and outside the global boundary and in the padding (either pointer may be null).
+// The update then is stencil.hpp leapfrog(cur, old, s, lamf[p]) and the first step first_step(φ, s, 0.5·lamf[p]): with
+// c ≡ 1 lamf[p] == Coeffs::lam and every bit is the constant-speed solve's. speed_cfl refuses courant()·max c > 1
+// unless `force`.
+struct SpeedRange {
+  double cmin = 0.0, cmax = 0.0;
+};
+SpeedRange speed_to_local(const Problem& p, const Layout& l, const double* c_global, double* lamf, double* c2);
+void speed_cfl(const Problem& p, const SpeedRange& r, bool force);
+
 
 // Error accumulator: L∞ and Σe² over the updated (interior) nodes.
 struct ErrAcc {
@@ -129,8 +146,9 @@ void cpu_init_first(const Layout& l, const Coeffs& c, const double* s, double* u
 // psi = nullptr: ψ = 0, its term skipped) over the whole allocation of the solve layout `l`, ghosts included; zeros on
 // and outside the global boundary and in the padding. phi / psi: local arrays in `src` = initial_layout(...), filled
 // by initial_to_local. With ψ absent and φ the eigenmode array, u1 equals cpu_init_first's bit for bit.
+// lamf != nullptr (a speed field, layout `l`): the node's coefficient is 0.5·lamf[p] (exact) instead of Coeffs::half_lam.
 void cpu_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
-                          const double* psi, double* u0, double* u1);
+                          const double* psi, double* u0, double* u1, const double* lamf = nullptr);
 
 // Discrete energy of two stored levels a = u^n, b = u^{n+1} (leapfrog conserves it exactly in exact arithmetic):
 //   E^{n+1/2} = V/2 · [ Σ ((b − a)/τ)² + Σ_d (1/h_d²) Σ_{edges (p,q) along d} (b_p − b_q)(a_p − a_q) ],  V = hx·hy·hz,
@@ -144,7 +162,11 @@ struct EnergySums {
   double abs = 0.0;             // Σ |kinetic term| + Σ |each edge product|: the scale of the summation error
   i64 depth = 0;
 };
-EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double* a, const double* b);
+// c2 != nullptr (a speed field, layout `l`): the conserved quantity carries the mass weight, kinetic term
+// ((b − a)·(1/τ))² / c2[p] at every node with c2[p] > 0 (the global interior; elsewhere b − a = 0); the potential term is
+// unchanged. c2 == nullptr: the code path and its bits are what they were.
+EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double* a, const double* b,
+                      const double* c2 = nullptr);
 inline double energy_value(const Problem& p, double kin, double pot) {
   return (0.5 * ((p.hx() * p.hy()) * p.hz())) * (kin + pot);
 }
@@ -153,8 +175,10 @@ inline double energy_value(const Problem& p, double kin, double pot) {
 // If acc != nullptr also accumulates the error vs the analytic solution φ·ct over the box.
 // sponge != nullptr: the damped update (stencil.hpp leapfrog_damped) with the node's g = max, r = min of the three 1-D
 // tables (problem.hpp sponge_tables; global indices); a node with g = 0 gets the undamped bits.
+// lamf != nullptr: a speed field (speed_to_local, layout `l`) — the coefficient of node p is lamf[p] instead of Coeffs::lam.
 void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox& box,
-                  const double* s, double ct, ErrAcc* acc, const SpongeView* sponge = nullptr);
+                  const double* s, double ct, ErrAcc* acc, const SpongeView* sponge = nullptr,
+                  const double* lamf = nullptr);
 
 // Sponge layers and the fused passes. An undamped pass of `steps` steps from damped levels u^{n−1}, u^n differs from
 // the damped one only within reach of the layers: u^{n+steps} on the slabs d < W + steps − 1 from each damped face (d:
@@ -269,6 +293,14 @@ class CpuSolver {
   // values ignored; psi_global = nullptr: ψ = 0): u⁰, u¹ by cpu_first_step_field, then the ordinary steps from n = 1.
   // The error columns then are the difference from the eigenmode. It and set_state replace each other.
   void set_initial(const double* phi_global, const double* psi_global);
+  // Variable wave speed: every following run() solves u_tt = c²(x)·Δu with c a global (N+1)³ field (speed_to_local; face
+  // values ignored, interior values finite and > 0; courant()·max c ≤ 1 unless `force`). nullptr clears it. The update
+  // takes its coefficient from lamf[p]; without set_initial the start is the eigenmode array through the first-step-field
+  // path (cpu_init_first's u⁰, and its u¹ where c = 1). Sources, receivers, sponge layers and set_state work as before;
+  // the error columns then mean nothing, and energy() carries the mass weight 1/c².
+  void set_speed(const double* c_global, bool force = false);
+  bool speed() const { return !lamf_.empty(); }
+  SpeedRange speed_range() const { return speed_range_; }
   // Receivers: R global nodes (ijk: R triples, each index in 0..N; duplicates allowed) whose value every following run()
   // reads from the stored field after the start and after every cpu_leapfrog step — the plain definition, the oracle
   // of the GPU record kernels. R = 0 removes them. traces(): the last run()'s (K+1) × R values, row n = u^n (NaN in the
@@ -307,6 +339,8 @@ class CpuSolver {
   Layout init_lay_;
   std::vector<double> init_[2];
   EnergySums e_start_;                   // of u⁰, u¹ of the last run() after set_initial
+  std::vector<double> lamf_, c2_;        // set_speed: lam·c² and c² in lay_ (empty: constant speed 1)
+  SpeedRange speed_range_;
   std::vector<i64> recv_off_;            // receivers: Layout::off of each node
   std::vector<double> traces_;           // [K + 1][R] of the last run()
   std::vector<i64> src_off_;             // sources: Layout::off of each node ...

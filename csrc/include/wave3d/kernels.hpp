@@ -42,8 +42,10 @@ void launch_init_two(const Layout& l, const Coeffs& c, const double* d_s, double
 // first_step / first_step_psi; psi = nullptr: ψ = 0, the term is skipped) over the WHOLE solve layout `l` — owned and
 // ghost nodes, exact zeros on and outside the global boundary, in the padding and the zero slot. phi / psi are device
 // buffers in `src` = make_layout(prob, box, 16, l.xg + 1, l.yg + 1, l.zg + 1) filled by initial_to_local (cpu.hpp).
+// lamf != nullptr (a speed field, cpu.hpp speed_to_local: device array in layout `l`): the VARC instantiation, the node's
+// coefficient is 0.5·lamf[p] — bit-identical to cpu_first_step_field with the same array.
 void launch_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
-                             const double* psi, double* u0, double* u1, hipStream_t stream);
+                             const double* psi, double* u0, double* u1, hipStream_t stream, const double* lamf = nullptr);
 
 // Discrete energy of two stored levels a = u^n, b = u^{n+1} over the owned nodes of `l` (cpu.hpp cpu_energy has the
 // formula; edges to the upper neighbours read the ghost layer, so the fields must be valid there: one rank, or fresh
@@ -88,9 +90,14 @@ void launch_source_cone(const Layout& l, const Coeffs& c, double* out_prev, doub
 // per workgroup into partials[0 .. leapfrog_blocks()).
 // sponge != nullptr: the damped step of the sponge layers (the DAMP instantiations; the tables live in device memory,
 // problem.hpp SpongeView); bit-identical to cpu_leapfrog with the same tables.
+// lamf != nullptr: a speed field (cpu.hpp speed_to_local; device array in layout `l`): the VARC instantiations, which
+// load the thread's lamf pair one plane ahead with the plane's other loads (32 instead of 24 bytes per node);
+// bit-identical to cpu_leapfrog with the same array. Not with 8 rows per wave; with a sponge at 1 or 2 rows (and the LDS
+// variant) only — leapfrog_speed_supported says which, launch_leapfrog refuses the rest.
+bool leapfrog_speed_supported(const LeapfrogTiling& t, bool sponge);
 void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox* boxes, int nbox,
                      const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream,
-                     const SpongeView* sponge = nullptr);
+                     const SpongeView* sponge = nullptr, const double* lamf = nullptr);
 
 // Sponge layers on the fused schedule (kernels_sponge.hip). An LDS pass of `steps` steps runs undamped; its two stored
 // outputs differ from the damped levels only on the slabs cpu.hpp sponge_boxes returns, which this recomputes from the
@@ -114,7 +121,9 @@ void launch_sponge_box(const Layout& l, const Coeffs& c, const SpongeView& table
 int leapfrog2_partials(const Layout& l, const LBox& box, const Leapfrog2Tiling& t);
 void launch_leapfrog2(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
                       double* out2, const LBox& box, const double* d_s, double ct2, Partial* partials,
-                      const Leapfrog2Tiling& t, hipStream_t stream, i64 sx0 = 1, i64 sx1 = 0);
+                      const Leapfrog2Tiling& t, hipStream_t stream, i64 sx0 = 1, i64 sx1 = 0, const double* lamf = nullptr);
+// (lamf != nullptr: a speed field in layout `l` — both stages, the recomputed halo rows and the spare z lanes read lamf at
+// their own node: 20 instead of 16 bytes per node-step; bit-identical to two cpu_leapfrog steps with the same array)
 
 // Deep temporal blocking: S = 2..4 leapfrog steps in one pass, all intermediate levels in LDS (32 × 32 (y,z) tiles
 // marching in x (or in x chunks when the tiles alone do not fill the GPU), one workgroup per CU). Reads u^{n−1}, u^n;

@@ -57,7 +57,8 @@ struct HostColl {
 // ---- field dumps / checkpoints (runtime_io.cpp) -------------------------------------------------------------------
 // PREFIX[.rankR].bin (raw little-endian fp64, C order [x][y][z], owned nodes) + .json sidecar (wave3d-dump-v1).
 void write_dump(const std::string& prefix, const Problem& p, const Layout& l, const std::vector<double>& u, int rank,
-                int world, const Dims& d, int step = -1);
+                int world, const Dims& d, int step = -1, const SpeedRange* speed = nullptr);
+// (speed: the sidecar names a speed field — "speed": [min c, max c] — only when one is set)
 // u^K → PREFIX.cur, u^{K−1} → PREFIX.prev
 void write_checkpoint(const std::string& prefix, const Problem& p, const Layout& l, const std::vector<double>& cur,
                       const std::vector<double>& prev, int rank, int world, const Dims& d);
@@ -70,6 +71,8 @@ int load_dump_global(const std::string& prefix, const Problem& p, std::vector<do
 // PREFIX.phi → φ = u(·,0) and, when it exists, PREFIX.psi → ψ = u_t(·,0) (else psi is left empty): the same format and
 // the same N / tau / L / box checks as a checkpoint's dumps (refusals start with "initial:")
 void load_initial(const std::string& prefix, const Problem& p, std::vector<double>& phi, std::vector<double>& psi);
+// PREFIX.c → the speed field c(x) of --speed: the same format and checks (refusals start with "speed:")
+void load_speed(const std::string& prefix, const Problem& p, std::vector<double>& c);
 // Receivers (--receivers FILE, --traces OUT). FILE: text, one "i j k" per line (global node indices; blank lines and
 // lines starting with # are skipped); returns the 3·R indices. OUT.bin: raw little-endian fp64, C order [K+1][R], row n
 // = u^n at the R nodes; OUT.json: {"format": "wave3d-traces-v1", "dtype", "order", "N", "K", "L" [, "box"], "tau",

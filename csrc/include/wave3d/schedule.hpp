@@ -175,7 +175,13 @@ struct UnitPlan {
 // The units of a solve that starts at level start_n (1, 2 or a resumed step); analytic: the first is an analytic start.
 // sources: point sources are set (plan_sources) — the last unit then keeps both levels (no drop_prev: the correction is
 // added to the stored u^K after the pass, and rebuilding u^{K−1} would run the pass over it again).
-std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources = false);
+// speed: a coefficient field is set (SpeedPlan). One rank's fused-single mode then runs single steps and k_leapfrog2 pairs
+// wherever the intermediate step needs no check — the tb = false unit list, whatever `tb` says, because only those
+// kernels read a coefficient per node — or single steps only (receivers, sources or a sponge are set too: the cone
+// kernels and k_sponge_box recompute with the constant operator). No unit gets drop_prev.
+enum class SpeedPlan { kNone = 0, kPairs = 1, kSingles = 2 };
+std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources = false,
+                                 SpeedPlan speed = SpeedPlan::kNone);
 
 // --poison-ghosts where the messages land in the field buffers themselves (every schedule but the 3-D block passes,
 // whose receive regions k_box_copy fills): what a unit's exchange NaN-fills. `rows` runs of `count` doubles, `pitch`
@@ -215,7 +221,8 @@ std::vector<LinkPlan> plan_links(const RankSchedule& s);
 struct Traffic {
   double field_bytes = 0.0, halo_bytes = 0.0;
 };
-Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool init_kernel);
+// speed: every unit and the first-step kernel also read the coefficient field once over the compute box.
+Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool init_kernel, bool speed = false);
 
 // Receivers: grid nodes whose value u^n is recorded for every n = 0..K. `nodes` holds R global (i, j, k) triples, each
 // index in 0..N; slot r of a trace row is node r of the list (a node listed twice fills two slots with the same values).

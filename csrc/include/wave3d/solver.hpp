@@ -166,6 +166,22 @@ class GpuSolver {
   // transports, tb = false (k_leapfrog2 pairs), and a receiver or source within W + temporal nodes of a damped face (the
   // cone kernels recompute with the undamped operator, which equals the damped one only outside that reach).
   bool sponge() const { return sch_.prob.sponge.on(); }
+  // Variable wave speed u_tt = c²(x)·Δu (cpu.hpp speed_to_local; CpuSolver is the definition, the fields match it bit for
+  // bit). c: a global (N+1)³ field, face values ignored, interior values finite and > 0; courant()·max c ≤ 1 unless
+  // `force`; nullptr clears it. lamf = lam·c² is a fifth device buffer in the solve layout, refused when it does not fit
+  // into free device memory. The LDS pass kernels are untouched: a solve with a speed field runs the VARC instantiations
+  // of the single-step kernels and of k_leapfrog2_rq — single steps and two-step pairs (the tb = false unit list,
+  // whatever `tb` says); single steps only with receivers, sources or a sponge (the cone kernels and k_sponge_box
+  // recompute with the constant operator; k_record_gather and the one-step source add are coefficient-free). The start is
+  // stored by k_first_step_field<VARC> from step 1 — from set_initial's φ, ψ, else from the eigenmode array kept in
+  // init_[0] (no analytic start, no init2); no drop_prev. Everything is on s0, graph-captured, run_batch pipelined.
+  // Dropping or setting it drops the captured graph. Refused (messages start with "speed:"): a world larger than 1 of any
+  // kind, fake ranks, the push and copy-engine transports, 8 rows per wave (4 with a sponge), set_state, temporal = 3 or 4
+  // (the default 5 stands for "unset" and runs pairs), and energy() — Solver.energy downloads both levels and runs
+  // cpu_energy with the mass weight.
+  void set_speed(const double* c_global, bool force = false);
+  bool speed() const { return lamf_dev_ != nullptr; }
+  SpeedRange speed_range() const { return speed_range_; }
   // Discrete energy (cpu.hpp cpu_energy): which = 0: E^{K−1/2} of the retained u^{K−1}, u^K; which = 1: E^{1/2},
   // computed inside the solve right after the first-step kernel (solves started by set_initial) and kept on the
   // device. One rank only. energy_sums: the kinetic and potential sums themselves.
@@ -212,7 +228,7 @@ class GpuSolver {
   std::string transport() const;
   // Bytes the last run() moved (schedule.hpp traffic; units_ is rebuilt at the start of every solve)
   using Traffic = wave3d::Traffic;
-  Traffic traffic() const { return wave3d::traffic(sch_, units_, !analytic_ && resume_n_ == 0); }
+  Traffic traffic() const { return wave3d::traffic(sch_, units_, !analytic_ && resume_n_ == 0, speed()); }
   // whether the last solve's passes stored u^{K−1} themselves (false: its last pass left it out, UnitPlan::drop_prev,
   // and the first of energy(0), download(1), field_hash(1) rebuilds it)
   bool stored_prev() const { return units_.empty() || !units_.back().drop_prev; }
@@ -340,6 +356,13 @@ class GpuSolver {
   // u^{n+s}, on s0
   void source_correct(const UnitPlan* u, double* prev, double* last);
   void source_finish();  // end of the solve: the last unit's correction
+  double* lamf_dev_ = nullptr;        // set_speed: lam·c² in the solve layout (null: constant speed 1)
+  SpeedRange speed_range_;
+  int temporal_asked_ = 0;            // SolverOptions::temporal as given (sch_.opt.temporal may be lowered)
+  bool speed_eig_ = false;            // init_[0] holds the eigenmode array set_speed put there (no set_initial yet)
+  SpeedPlan speed_plan() const {
+    return !speed() ? SpeedPlan::kNone : (recording_ || n_src_ > 0 || sponge()) ? SpeedPlan::kSingles : SpeedPlan::kPairs;
+  }
   double* sponge_dev_ = nullptr;      // sponge layers: the six tables (N + 3 entries each) in device memory ...
   SpongeView sponge_view_;            // ... and their node-0 pointers
   std::vector<LBox> sponge_boxes_[6]; // ... and the slabs a fused unit of s = 2..5 steps recomputes (cpu.hpp sponge_boxes)

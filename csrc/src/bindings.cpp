@@ -398,9 +398,28 @@ PYBIND11_MODULE(_C, m) {
     initial_to_local(src, gp, out.mutable_data());
     return out;
   }, py::arg("layout"), py::arg("field"), "a GLOBAL (N+1)^3 field sliced into `layout`, the six global faces zeroed");
+  m.def("speed_to_local", [](const Problem& p, const Layout& l, const darr& c) {
+    const i64 n = p.N + 1;
+    const double* cp = ro_ptr(c, n * n * n, "c");
+    darr lamf(static_cast<py::ssize_t>(l.total)), c2(static_cast<py::ssize_t>(l.total));
+    const SpeedRange r = speed_to_local(p, l, cp, lamf.mutable_data(), c2.mutable_data());
+    return py::make_tuple(lamf, c2, r.cmin, r.cmax);
+  }, py::arg("problem"), py::arg("layout"), py::arg("c"),
+        "a GLOBAL (N+1)^3 speed field as (lamf = lam c^2, c2 = c^2) in `layout` (zeros outside the global interior) and "
+        "the interior minimum and maximum of c; refuses non-finite or non-positive interior values");
+  m.def("eigenmode_local", [](const Problem& p, const Layout& src) {
+    const std::vector<double> v = eigenmode_local(p, src);
+    return darr(static_cast<py::ssize_t>(v.size()), v.data());
+  }, py::arg("problem"), py::arg("layout"));
   m.def("cpu_first_step_field",
         [](const Layout& l, const Layout& src, const Coeffs& c, double tau, const darr& phi, py::object psi, darr u0,
-           darr u1) {
+           darr u1, py::object lamf) {
+          darr lamf_a;
+          const double* lp = nullptr;
+          if (!lamf.is_none()) {
+            lamf_a = lamf.cast<darr>();
+            lp = ro_ptr(lamf_a, l.total, "lamf");
+          }
           const double* fp = ro_ptr(phi, src.total, "phi");
           const double* sp = nullptr;
           darr psi_a;
@@ -411,13 +430,20 @@ PYBIND11_MODULE(_C, m) {
           double* a = mut_ptr(u0, l.total, "u0");
           double* b = mut_ptr(u1, l.total, "u1");
           py::gil_scoped_release nogil;
-          cpu_first_step_field(l, src, c, tau, fp, sp, a, b);
+          cpu_first_step_field(l, src, c, tau, fp, sp, a, b, lp);
         },
         py::arg("layout"), py::arg("src"), py::arg("coeffs"), py::arg("tau"), py::arg("phi"), py::arg("psi"),
-        py::arg("u0"), py::arg("u1"));
+        py::arg("u0"), py::arg("u1"), py::arg("lamf") = py::none());
   m.def("cpu_energy",
-        [](const Problem& p, const Layout& l, const darr& a, const darr& b) {
-          const EnergySums e = cpu_energy(l, Coeffs::from(p), p.tau, ro_ptr(a, l.total, "a"), ro_ptr(b, l.total, "b"));
+        [](const Problem& p, const Layout& l, const darr& a, const darr& b, py::object c2) {
+          darr c2_a;  // c2: speed_to_local's c^2 array in `layout` (the mass weight 1/c^2 of the kinetic term)
+          const double* c2p = nullptr;
+          if (!c2.is_none()) {
+            c2_a = c2.cast<darr>();
+            c2p = ro_ptr(c2_a, l.total, "c2");
+          }
+          const EnergySums e =
+              cpu_energy(l, Coeffs::from(p), p.tau, ro_ptr(a, l.total, "a"), ro_ptr(b, l.total, "b"), c2p);
           const double half_v = 0.5 * ((p.hx() * p.hy()) * p.hz());
           py::dict d;
           d["E"] = energy_value(p, e.kin, e.pot);
@@ -427,15 +453,21 @@ PYBIND11_MODULE(_C, m) {
           d["depth"] = e.depth;
           return d;
         },
-        py::arg("problem"), py::arg("layout"), py::arg("a"), py::arg("b"),
+        py::arg("problem"), py::arg("layout"), py::arg("a"), py::arg("b"), py::arg("c2") = py::none(),
         "discrete energy of a = u^n, b = u^{n+1} (local arrays in `layout`): E, its kinetic / potential sums, "
         "abs_terms = V/2 * sum |terms| (the scale of the summation error) and the summation depth");
   m.def("energy_value", &energy_value);
   m.def(
       "cpu_leapfrog",
       [](const Layout& l, const Coeffs& c, const darr& cur, darr old, const LBox& box, const darr& s, double ct,
-         bool check, py::object sponge) -> py::object {
+         bool check, py::object sponge, py::object lamf) -> py::object {
         const double* cp = ro_ptr(cur, l.total, "cur");
+        darr lamf_a;  // lamf: a speed field's lam c^2 array in `layout`
+        const double* lp = nullptr;
+        if (!lamf.is_none()) {
+          lamf_a = lamf.cast<darr>();
+          lp = ro_ptr(lamf_a, l.total, "lamf");
+        }
         double* op = mut_ptr(old, l.total, "old");
         const double* sp = ro_ptr(s, l.N + 3, "s") + 1;
         SpongeTables tab;  // sponge: a Problem whose sponge_tables give the damped step
@@ -447,13 +479,13 @@ PYBIND11_MODULE(_C, m) {
         ErrAcc acc;
         {
           py::gil_scoped_release nogil;
-          cpu_leapfrog(l, c, cp, op, box, sp, ct, check ? &acc : nullptr, sponge.is_none() ? nullptr : &view);
+          cpu_leapfrog(l, c, cp, op, box, sp, ct, check ? &acc : nullptr, sponge.is_none() ? nullptr : &view, lp);
         }
         if (!check) return py::none();
         return py::make_tuple(acc.max, acc.sum);
       },
       py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("old"), py::arg("box"), py::arg("s"),
-      py::arg("ct") = 0.0, py::arg("check") = false, py::arg("sponge") = py::none());
+      py::arg("ct") = 0.0, py::arg("check") = false, py::arg("sponge") = py::none(), py::arg("lamf") = py::none());
   m.def("cpu_error", [](const Layout& l, const darr& u, const LBox& box, const darr& s, double ct) {
     ErrAcc acc;
     cpu_error(l, ro_ptr(u, l.total, "u"), box, ro_ptr(s, l.N + 3, "s") + 1, ct, &acc);
@@ -503,6 +535,16 @@ PYBIND11_MODULE(_C, m) {
         if (!psi.is_none()) psi_a = psi.cast<darr>();
         s.set_initial(ro_ptr(phi, n * n * n, "phi"), psi.is_none() ? nullptr : ro_ptr(psi_a, n * n * n, "psi"));
       }, py::arg("phi"), py::arg("psi") = py::none())
+      .def("set_speed", [](CpuSolver& s, py::object c, bool force) {
+        if (c.is_none()) return s.set_speed(nullptr);
+        const i64 n = s.layout().N + 1;
+        const darr c_a = c.cast<darr>();
+        s.set_speed(ro_ptr(c_a, n * n * n, "c"), force);
+      }, py::arg("c"), py::arg("force") = false, "solve u_tt = c(x)^2 Lap u with this global (N+1)^3 field (None clears it)")
+      .def_property_readonly("speed", &CpuSolver::speed)
+      .def_property_readonly("speed_range", [](const CpuSolver& s) {
+        return py::make_tuple(s.speed_range().cmin, s.speed_range().cmax);
+      })
       .def("set_receivers", [](CpuSolver& s, const iarr& nodes) {
         int R = 0;
         const i64* p = receiver_ptr(nodes, &R);
@@ -578,12 +620,13 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("gpu_first_step_field",
         [](const Layout& l, const Layout& src, const Coeffs& c, double tau, std::uintptr_t phi, std::uintptr_t psi,
-           std::uintptr_t u0, std::uintptr_t u1, std::uintptr_t stream) {
+           std::uintptr_t u0, std::uintptr_t u1, std::uintptr_t stream, std::uintptr_t lamf) {
           launch_first_step_field(l, src, c, tau, dptr<const double>(phi), dptr<const double>(psi), dptr<double>(u0),
-                                  dptr<double>(u1), sptr(stream));
+                                  dptr<double>(u1), sptr(stream), dptr<const double>(lamf));
         },
         py::arg("layout"), py::arg("src"), py::arg("coeffs"), py::arg("tau"), py::arg("phi"), py::arg("psi"),
-        py::arg("u0"), py::arg("u1"), py::arg("stream"), "k_first_step_field (psi = 0: no psi term)");
+        py::arg("u0"), py::arg("u1"), py::arg("stream"), py::arg("lamf") = 0,
+        "k_first_step_field (psi = 0: no psi term; lamf: a speed field's device array in `layout`)");
   // receivers: the table is `count` rows of plan_receivers' array in device memory (a Receiver is its five int64s)
   m.def("gpu_record_cone",
         [](const Layout& l, const Coeffs& c, std::uintptr_t prev, std::uintptr_t cur, int n, int steps,
@@ -646,8 +689,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("gpu_leapfrog",
         [](const Layout& l, const Coeffs& c, std::uintptr_t cur, std::uintptr_t old, const std::vector<LBox>& boxes,
            std::uintptr_t s, double ct, std::uintptr_t partials, const LeapfrogTiling& t, std::uintptr_t stream,
-           std::uintptr_t sponge) {
-          // sponge: sponge_tables' (6, N + 3) array in device memory (0: the undamped step)
+           std::uintptr_t sponge, std::uintptr_t lamf) {
+          // sponge: sponge_tables' (6, N + 3) array in device memory (0: the undamped step); lamf: a speed field's
+          // device array in `layout` (0: constant speed)
           SpongeView view;
           if (sponge) {
             const i64 n = l.N + 3;
@@ -656,10 +700,12 @@ PYBIND11_MODULE(_C, m) {
           }
           launch_leapfrog(l, c, dptr<const double>(cur), dptr<double>(old), boxes.data(),
                           static_cast<int>(boxes.size()), dptr<const double>(s) + 1, ct, dptr<Partial>(partials), t,
-                          sptr(stream), sponge ? &view : nullptr);
+                          sptr(stream), sponge ? &view : nullptr, dptr<const double>(lamf));
         },
         py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("old"), py::arg("boxes"), py::arg("s"),
-        py::arg("ct"), py::arg("partials"), py::arg("tiling"), py::arg("stream"), py::arg("sponge") = 0);
+        py::arg("ct"), py::arg("partials"), py::arg("tiling"), py::arg("stream"), py::arg("sponge") = 0,
+        py::arg("lamf") = 0);
+  m.def("gpu_leapfrog_speed_supported", &leapfrog_speed_supported, py::arg("tiling"), py::arg("sponge"));
   m.def("gpu_sponge_box",
         [](const Layout& l, const Coeffs& c, std::uintptr_t tables, std::uintptr_t prev, std::uintptr_t cur,
            std::uintptr_t out1, std::uintptr_t out2, const LBox& box, int steps, std::uintptr_t stream) {
@@ -685,14 +731,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("gpu_leapfrog2",
         [](const Layout& l, const Coeffs& c, std::uintptr_t prev, std::uintptr_t cur, std::uintptr_t out1,
            std::uintptr_t out2, const LBox& box, std::uintptr_t s, double ct2, std::uintptr_t partials,
-           const Leapfrog2Tiling& t, std::uintptr_t stream, i64 sx0, i64 sx1) {
+           const Leapfrog2Tiling& t, std::uintptr_t stream, i64 sx0, i64 sx1, std::uintptr_t lamf) {
           launch_leapfrog2(l, c, dptr<const double>(prev), dptr<const double>(cur), dptr<double>(out1),
                            dptr<double>(out2), box, dptr<const double>(s) + 1, ct2, dptr<Partial>(partials), t,
-                           sptr(stream), sx0, sx1);
+                           sptr(stream), sx0, sx1, dptr<const double>(lamf));
         },
         py::arg("layout"), py::arg("coeffs"), py::arg("prev"), py::arg("cur"), py::arg("out1"), py::arg("out2"),
         py::arg("box"), py::arg("s"), py::arg("ct2"), py::arg("partials"), py::arg("tiling"), py::arg("stream"),
-        py::arg("sx0") = 1, py::arg("sx1") = 0);
+        py::arg("sx0") = 1, py::arg("sx1") = 0, py::arg("lamf") = 0);
   py::class_<LeapfrogTbTiling>(m, "LeapfrogTbTiling")
       .def(py::init<>())
       .def_readwrite("stages", &LeapfrogTbTiling::stages)
@@ -943,6 +989,16 @@ PYBIND11_MODULE(_C, m) {
         if (!psi.is_none()) psi_a = psi.cast<darr>();
         s.set_initial(ro_ptr(phi, n * n * n, "phi"), psi.is_none() ? nullptr : ro_ptr(psi_a, n * n * n, "psi"));
       }, py::arg("phi"), py::arg("psi") = py::none())
+      .def("set_speed", [](GpuSolver& s, py::object c, bool force) {
+        if (c.is_none()) return s.set_speed(nullptr);
+        const i64 n = s.problem().N + 1;
+        const darr c_a = c.cast<darr>();
+        s.set_speed(ro_ptr(c_a, n * n * n, "c"), force);
+      }, py::arg("c"), py::arg("force") = false, "solve u_tt = c(x)^2 Lap u with this global (N+1)^3 field (None clears it)")
+      .def_property_readonly("speed", &GpuSolver::speed)
+      .def_property_readonly("speed_range", [](const GpuSolver& s) {
+        return py::make_tuple(s.speed_range().cmin, s.speed_range().cmax);
+      })
       .def("set_receivers", [](GpuSolver& s, const iarr& nodes) {
         int R = 0;
         const i64* p = receiver_ptr(nodes, &R);

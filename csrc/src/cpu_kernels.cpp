@@ -53,8 +53,28 @@ void cpu_init_first(const Layout& l, const Coeffs& c, const double* s, double* u
   }
 }
 
+std::vector<double> eigenmode_local(const Problem& p, const Layout& l) {
+  const std::vector<double> tab = sin_table_ext(p);
+  const double* s = tab.data() + 1;
+  std::vector<double> out(static_cast<size_t>(l.total), 0.0);
+#pragma omp parallel for schedule(static)
+  for (i64 x = -l.xg; x < l.nx + l.xg; ++x) {
+    const i64 gx = l.gx0 + x;
+    if (gx < 0 || gx > l.N) continue;
+    for (i64 y = -l.yg; y < l.ny + l.yg; ++y) {
+      const i64 gy = l.gy0 + y;
+      if (gy < 0 || gy > l.N) continue;
+      for (i64 z = -l.zg; z < l.nz + l.zg; ++z) {
+        const i64 gz = l.gz0 + z;
+        if (gz >= 0 && gz <= l.N) out[static_cast<size_t>(l.off(x, y, z))] = phi(s, gx, gy, gz);
+      }
+    }
+  }
+  return out;
+}
+
 void cpu_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
-                          const double* psi, double* u0, double* u1) {
+                          const double* psi, double* u0, double* u1, const double* lamf) {
   W3D_REQUIRE(src.xg == l.xg + 1 && src.yg == l.yg + 1 && src.zg == l.zg + 1 && src.nx == l.nx && src.ny == l.ny &&
                   src.nz == l.nz && src.gx0 == l.gx0 && src.gy0 == l.gy0 && src.gz0 == l.gz0,
               "first step: the source layout must be the solve layout's box with one ghost layer more");
@@ -82,7 +102,7 @@ void cpu_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, d
         if (gx > 0 && gx < N && gy > 0 && gy < N && gz > 0 && gz < N) {
           const double lap = c.box ? d2sum_box(v, f[-P], f[P], f[-R], f[R], f[-1], f[1], c.ry, c.rz)
                                    : d2sum(v, f[-P], f[P], f[-R], f[R], f[-1], f[1]);
-          double w = first_step(v, lap, c.half_lam);
+          double w = first_step(v, lap, lamf ? 0.5 * lamf[o] : c.half_lam);
           if (psi) w = first_step_psi(w, psi[src.off(ix, iy, iz)], tau);
           u1[o] = w;
         }
@@ -91,7 +111,7 @@ void cpu_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, d
   }
 }
 
-EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double* a, const double* b) {
+EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double* a, const double* b, const double* c2) {
   EnergySums out;
   if (l.nx <= 0 || l.ny <= 0 || l.nz <= 0) return out;
   W3D_REQUIRE(l.xg >= 1 && l.yg >= 1 && l.zg >= 1, "energy: the layout needs a ghost layer");
@@ -106,12 +126,13 @@ EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double
       const bool ey = l.gy0 + iy + 1 <= N;
       const double* ra = a + l.off(ix, iy, 0);
       const double* rb = b + l.off(ix, iy, 0);
+      const double* rc = c2 ? c2 + l.off(ix, iy, 0) : nullptr;  // (a speed field: the mass weight 1/c²)
       double kin = 0.0, pot = 0.0, ab = 0.0;
       for (i64 iz = 0; iz < l.nz; ++iz) {
         const bool ez = l.gz0 + iz + 1 <= N;
         const double av = ra[iz], bv = rb[iz];
         const double v = (bv - av) * inv_tau;
-        const double tk = v * v;
+        const double tk = !rc ? v * v : (rc[iz] > 0.0 ? (v * v) / rc[iz] : 0.0);
         const double tx = ex ? ((rb[iz + P] - bv) * (ra[iz + P] - av)) * c.ihx2 : 0.0;
         const double ty = ey ? ((rb[iz + R] - bv) * (ra[iz + R] - av)) * c.ihy2 : 0.0;
         const double tz = ez ? ((rb[iz + 1] - bv) * (ra[iz + 1] - av)) * c.ihz2 : 0.0;
@@ -136,9 +157,9 @@ EnergySums cpu_energy(const Layout& l, const Coeffs& c, double tau, const double
 
 namespace {
 
-template <bool CHECK, bool BOX, bool DAMP = false>
+template <bool CHECK, bool BOX, bool DAMP = false, bool VARC = false>
 void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* out, const LBox& b, const double* s,
-                   double ct, ErrAcc* acc, const SpongeView* sp = nullptr) {
+                   double ct, ErrAcc* acc, const SpongeView* sp = nullptr, const double* lamf = nullptr) {
   const i64 nxp = b.x1 - b.x0;
   std::vector<ErrAcc> part(CHECK ? static_cast<size_t>(nxp) : 0);
   const i64 P = l.plane, R = l.pitch;
@@ -153,11 +174,12 @@ void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* 
       const i64 row = l.off(ix, iy, 0);
       const double* cr = cur + row;
       double* orow = out + row;
+      const double* lrow = VARC ? lamf + row : nullptr;
       for (i64 iz = b.z0; iz < b.z1; ++iz) {
         const double u = cr[iz];
         const double lap = d2sum_t<BOX>(u, cr[iz - P], cr[iz + P], cr[iz - R], cr[iz + R], cr[iz - 1], cr[iz + 1],
                                         c.ry, c.rz);
-        double v = leapfrog(u, orow[iz], lap, c.lam);
+        double v = leapfrog(u, orow[iz], lap, VARC ? lrow[iz] : c.lam);
         if (DAMP) v = leapfrog_damped(v, orow[iz], std::fmax(gxy, sp->gz[l.gz0 + iz]), std::fmin(rxy, sp->rz[l.gz0 + iz]));
         orow[iz] = v;
         if (CHECK) {
@@ -179,10 +201,33 @@ void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* 
 
 }  // namespace
 
+namespace {
+// (a speed field: the same loops with the coefficient read per node)
+template <bool CHECK, bool BOX>
+void leapfrog_varc(const Layout& l, const Coeffs& c, const double* cur, double* out, const LBox& b, const double* s, double ct,
+                   ErrAcc* acc, const SpongeView* sp, const double* lamf) {
+  if (sp)
+    leapfrog_impl<CHECK, BOX, true, true>(l, c, cur, out, b, s, ct, acc, sp, lamf);
+  else
+    leapfrog_impl<CHECK, BOX, false, true>(l, c, cur, out, b, s, ct, acc, nullptr, lamf);
+}
+}  // namespace
+
 void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox& box,
-                  const double* s, double ct, ErrAcc* acc, const SpongeView* sponge) {
+                  const double* s, double ct, ErrAcc* acc, const SpongeView* sponge, const double* lamf) {
   if (box.empty()) return;
-  if (sponge) {  // (sponge layers: the same loop with the damped update)
+  if (lamf) {
+    if (c.box) {
+      if (acc)
+        leapfrog_varc<true, true>(l, c, cur, old_out, box, s, ct, acc, sponge, lamf);
+      else
+        leapfrog_varc<false, true>(l, c, cur, old_out, box, s, ct, nullptr, sponge, lamf);
+    } else if (acc) {
+      leapfrog_varc<true, false>(l, c, cur, old_out, box, s, ct, acc, sponge, lamf);
+    } else {
+      leapfrog_varc<false, false>(l, c, cur, old_out, box, s, ct, nullptr, sponge, lamf);
+    }
+  } else if (sponge) {  // (sponge layers: the same loop with the damped update)
     if (c.box) {
       if (acc)
         leapfrog_impl<true, true, true>(l, c, cur, old_out, box, s, ct, acc, sponge);

@@ -63,6 +63,72 @@ void initial_to_local(const Layout& l, const double* g, double* out) {
   }
 }
 
+SpeedRange speed_to_local(const Problem& p, const Layout& l, const double* c, double* lamf, double* c2) {
+  W3D_REQUIRE(c != nullptr, "speed: no coefficient field");
+  const i64 N = p.N, n1 = N + 1;
+  SpeedRange r;
+  bool bad = false;
+  double lo = HUGE_VAL, hi = 0.0;
+  // every rank checks the whole global interior, so a refusal and the range do not depend on the decomposition
+#pragma omp parallel for schedule(static) reduction(min : lo) reduction(max : hi) reduction(|| : bad)
+  for (i64 x = 1; x < N; ++x)
+    for (i64 y = 1; y < N; ++y)
+      for (i64 z = 1; z < N; ++z) {
+        const double v = c[(x * n1 + y) * n1 + z];
+        if (!(std::isfinite(v) && v > 0.0)) bad = true;
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+      }
+  W3D_REQUIRE(!bad, "speed: every interior value of c must be finite and > 0");
+  r.cmin = lo;
+  r.cmax = hi;
+  const double lam = Coeffs::from(p).lam;
+  for (double* out : {lamf, c2})
+    if (out) std::fill(out, out + l.total, 0.0);
+#pragma omp parallel for schedule(static)
+  for (i64 x = -l.xg; x < l.nx + l.xg; ++x) {
+    const i64 gx = l.gx0 + x;
+    if (gx <= 0 || gx >= N) continue;
+    for (i64 y = -l.yg; y < l.ny + l.yg; ++y) {
+      const i64 gy = l.gy0 + y;
+      if (gy <= 0 || gy >= N) continue;
+      for (i64 z = -l.zg; z < l.nz + l.zg; ++z) {
+        const i64 gz = l.gz0 + z;
+        if (gz <= 0 || gz >= N) continue;
+        const double v = c[(gx * n1 + gy) * n1 + gz];
+        const double v2 = v * v;
+        const i64 o = l.off(x, y, z);
+        if (c2) c2[o] = v2;
+        if (lamf) lamf[o] = lam * v2;
+      }
+    }
+  }
+  return r;
+}
+
+void speed_cfl(const Problem& p, const SpeedRange& r, bool force) {
+  const double cn = p.courant() * r.cmax;
+  W3D_REQUIRE(force || cn <= 1.0, "speed: CFL violated: courant * max c = " + std::to_string(cn) +
+                                      " > 1 (max c = " + std::to_string(r.cmax) + "); use a smaller tau, or force");
+}
+
+void CpuSolver::set_speed(const double* c, bool force) {
+  if (!c) {
+    lamf_.clear();
+    c2_.clear();
+    speed_range_ = SpeedRange{};
+    runs_ = 0;
+    return;
+  }
+  std::vector<double> lamf(static_cast<size_t>(lay_.total)), c2(static_cast<size_t>(lay_.total));
+  const SpeedRange r = speed_to_local(prob_, lay_, c, lamf.data(), c2.data());
+  speed_cfl(prob_, r, force);
+  lamf_ = std::move(lamf);
+  c2_ = std::move(c2);
+  speed_range_ = r;
+  runs_ = 0;
+}
+
 void CpuSolver::set_initial(const double* phi, const double* psi) {
   W3D_REQUIRE(1 < prob_.K, "resume step must be in [1, K)");
   init_lay_ = initial_layout(prob_, lay_);
@@ -84,10 +150,10 @@ EnergySums CpuSolver::energy_sums(int which) const {
   W3D_REQUIRE(which == 0 || which == 1, "energy: which is 0 (E at K-1/2) or 1 (E at 1/2)");
   W3D_REQUIRE(runs_ > 0, "energy: no solve has run yet");
   if (which == 1) {
-    W3D_REQUIRE(initial_, "energy: E(1/2) is kept by solves that start from set_initial");
+    W3D_REQUIRE(initial_ || speed(), "energy: E(1/2) is kept by solves that start from set_initial");
     return e_start_;
   }
-  return cpu_energy(lay_, Coeffs::from(prob_), prob_.tau, field(1).data(), field(0).data());
+  return cpu_energy(lay_, Coeffs::from(prob_), prob_.tau, field(1).data(), field(0).data(), speed() ? c2_.data() : nullptr);
 }
 
 double CpuSolver::energy(int which) const {
@@ -165,6 +231,7 @@ CpuResult CpuSolver::run() {
   // sponge layers: every step is the damped one (cpu_leapfrog's table argument); the start levels are what they are
   const SpongeView sponge_view = prob_.sponge.on() ? sponge_.view() : SpongeView{};
   const SpongeView* sp = prob_.sponge.on() ? &sponge_view : nullptr;
+  const double* lamf = speed() ? lamf_.data() : nullptr;  // (a speed field: the coefficient per node)
   const LBox box = compute_box(lay_);
   const double n_int = static_cast<double>(prob_.N - 1);
   const double denom = n_int * n_int * n_int;
@@ -183,8 +250,14 @@ CpuResult CpuSolver::run() {
     u_[1] = resume_[1];
   } else if (initial_) {
     cpu_first_step_field(lay_, init_lay_, c, prob_.tau, init_[0].data(), init_[1].empty() ? nullptr : init_[1].data(),
-                         u_[0].data(), u_[1].data());
-    e_start_ = cpu_energy(lay_, c, prob_.tau, u_[0].data(), u_[1].data());
+                         u_[0].data(), u_[1].data(), lamf);
+    e_start_ = cpu_energy(lay_, c, prob_.tau, u_[0].data(), u_[1].data(), lamf ? c2_.data() : nullptr);
+  } else if (lamf) {
+    // a speed field without set_initial: the eigenmode array through the first-step-field path (u⁰ is cpu_init_first's)
+    const Layout il = initial_layout(prob_, lay_);
+    std::vector<double> phi0 = eigenmode_local(prob_, il);
+    cpu_first_step_field(lay_, il, c, prob_.tau, phi0.data(), nullptr, u_[0].data(), u_[1].data(), lamf);
+    e_start_ = cpu_energy(lay_, c, prob_.tau, u_[0].data(), u_[1].data(), c2_.data());
   } else {
     cpu_init_first(lay_, c, s, u_[0].data(), u_[1].data());
   }
@@ -216,10 +289,10 @@ CpuResult CpuSolver::run() {
     const double tc = now_s();
     if (is_check[static_cast<size_t>(n + 1)]) {
       ErrAcc a;
-      cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, time_factor(prob_, n + 1), &a, sp);
+      cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, time_factor(prob_, n + 1), &a, sp, lamf);
       record(n + 1, a);
     } else {
-      cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, 0.0, nullptr, sp);
+      cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, 0.0, nullptr, sp, lamf);
     }
     r.compute_s += now_s() - tc;
     std::swap(cur, old);

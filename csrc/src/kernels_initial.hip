@@ -42,6 +42,7 @@ struct FirstStepParams {
   i64 s_plane, s_pitch, s_zs;                               // source layout (ghost depths xg + 1, yg + 1, zg + 1)
   int pairs_per_row, pairs_per_plane;
   double half_lam, ry, rz, tau;
+  const double* lamf;  // VARC: lam·c² per node in the SOLVE layout (the pair at this thread's own store offset)
 };
 
 // One thread per 16-byte pair of the solve layout's plane blockIdx.y (k_init_first's grid). A pair with a valid node
@@ -52,6 +53,8 @@ struct FirstStepParams {
 // Cube and box share one code path: the kernel never reads Coeffs::box, it always evaluates d2sum_box with Coeffs::ry /
 // rz. For a cube Coeffs::from fills ry = rz = 1.0, and the box form fed ratios of 1 rounds exactly as d2sum does
 // (stencil.hpp), so the cube's bits depend on those two fields being 1.0 — as in k_init_first.
+// VARC: a speed field — the coefficient of a node is 0.5·lamf[p] (exact), the pair loaded at the thread's store offset.
+template <bool VARC>
 __global__ __launch_bounds__(256) void k_first_step_field(const FirstStepParams p) {
   const int q = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
   if (q >= p.pairs_per_plane) return;
@@ -83,13 +86,20 @@ __global__ __launch_bounds__(256) void k_first_step_field(const FirstStepParams 
     if (in[0] || in[1]) {
       const v2d xm = ld2(f - p.s_plane), xp = ld2(f + p.s_plane), ym = ld2(f - p.s_pitch), yp = ld2(f + p.s_pitch);
       double a[2] = {0.0, 0.0};
+      v2d hl;
+      hl.x = hl.y = p.half_lam;
+      if (VARC) {
+        const v2d lf = ld2(p.lamf + static_cast<i64>(blockIdx.y) * p.plane + 2 * static_cast<i64>(q));
+        hl.x = 0.5 * lf.x;
+        hl.y = 0.5 * lf.y;
+      }
       if (in[0]) {
         const double zm = f[-1];
-        a[0] = first_step(cv.x, d2sum_box(cv.x, xm.x, xp.x, ym.x, yp.x, zm, cv.y, p.ry, p.rz), p.half_lam);
+        a[0] = first_step(cv.x, d2sum_box(cv.x, xm.x, xp.x, ym.x, yp.x, zm, cv.y, p.ry, p.rz), hl.x);
       }
       if (in[1]) {
         const double zp = f[2];
-        a[1] = first_step(cv.y, d2sum_box(cv.y, xm.y, xp.y, ym.y, yp.y, cv.x, zp, p.ry, p.rz), p.half_lam);
+        a[1] = first_step(cv.y, d2sum_box(cv.y, xm.y, xp.y, ym.y, yp.y, cv.x, zp, p.ry, p.rz), hl.y);
       }
       if (p.psi) {
         const v2d sv = ld2(p.psi + so);
@@ -247,7 +257,7 @@ EnergyGrid energy_grid(const Layout& l) {
 }  // namespace
 
 void launch_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
-                             const double* psi, double* u0, double* u1, hipStream_t stream) {
+                             const double* psi, double* u0, double* u1, hipStream_t stream, const double* lamf) {
   W3D_REQUIRE(src.xg == l.xg + 1 && src.yg == l.yg + 1 && src.zg == l.zg + 1 && src.nx == l.nx && src.ny == l.ny &&
                   src.nz == l.nz && src.gx0 == l.gx0 && src.gy0 == l.gy0 && src.gz0 == l.gz0,
               "first step: the source layout must be the solve layout's box with one ghost layer more");
@@ -281,8 +291,12 @@ void launch_first_step_field(const Layout& l, const Layout& src, const Coeffs& c
   p.ry = c.ry;
   p.rz = c.rz;
   p.tau = tau;
+  p.lamf = lamf;
   const dim3 grid(static_cast<unsigned>(ceil_div(p.pairs_per_plane, 256)), static_cast<unsigned>(l.nx + 2 * l.xg));
-  hipLaunchKernelGGL(k_first_step_field, grid, dim3(256), 0, stream, p);
+  if (lamf)
+    hipLaunchKernelGGL(k_first_step_field<true>, grid, dim3(256), 0, stream, p);
+  else
+    hipLaunchKernelGGL(k_first_step_field<false>, grid, dim3(256), 0, stream, p);
   W3D_HIP_CHECK(hipGetLastError());
 }
 

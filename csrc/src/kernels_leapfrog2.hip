@@ -63,11 +63,17 @@ struct Lf2Params {
   double ihx2, ihy2, ihz2, tau2, ct2;
   // rectangular box: h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box; 1 for a cube — the same bits as d2sum)
   double ry, rz;
+  // a speed field (the VARC instantiations): lam·c² per node in the solve layout, offset like cur
+  const double* lamf;
   int ntz, nty, xchunk, ntiles, nblocks, xcd_remap;
 };
 
 // OCC > 1 asks the compiler for at least OCC waves per SIMD (fewer VGPRs, possibly some scratch spills)
-template <int R, bool CHECK, bool NT, int OCC>
+// VARC: a speed field — every node's coefficient is its own lamf value. Stage 1 (rows 1..E−2 of plane x, the recomputed
+// halo rows and the two spare z lanes included) reads the pair loaded one plane ahead with that row's u^{n−1} pair; stage 2
+// (rows 2..E−3 of plane x−1) reads the pair stage 1 used one iteration earlier, kept in registers: one more 16-byte load
+// per node and pass, 20 instead of 16 bytes per node-step. VARC = false keeps its code.
+template <int R, bool CHECK, bool NT, int OCC, bool VARC = false>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC))) void k_leapfrog2_rq(
     const Lf2Params p) {
   constexpr int E = R + 4;  // extended rows: e ↔ y = yt − 2 + e
@@ -127,6 +133,8 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC
   v2d m[E], c[E], q[E], o[E];
   // u^{n+1}: w1 = plane x−1 (rows 1..E−2), w2 = plane x−2 (rows 2..E−3)
   v2d w1[E], w2[E];
+  // lamf: lf = plane x (rows 1..E−2), lfp = plane x−1 (rows 2..E−3)
+  v2d lf[E], lfp[E];
   i64 px = xs * plane;  // plane base of x = xs − 1
 #pragma unroll
   for (int e = 0; e < E; ++e) {
@@ -136,12 +144,15 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC
     o[e] = z2;
     w1[e] = z2;
     w2[e] = z2;
+    lf[e] = z2;
+    lfp[e] = z2;
     if (rl[e]) {
       c[e] = ld2(cur + (px + rb[e]) + lo);
       if (e >= 1 && e <= E - 2) {
         m[e] = ld2(cur + (px - plane + rb[e]) + lo);
         q[e] = ld2(cur + (px + plane + rb[e]) + lo);
         o[e] = ld2(prev + (px + rb[e]) + lo);
+        if (VARC) lf[e] = ld2(p.lamf + (px + rb[e]) + lo);
       }
     }
   }
@@ -159,16 +170,18 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC
   for (i64 x = xs - 1; x <= xe; ++x, px += plane) {
     const bool more = x + 1 <= xe;
     // ---- prefetch for the next plane (consumed next iteration; vector-memory completion is in order)
-    v2d nq[E], nc[E], no[E];
+    v2d nq[E], nc[E], no[E], nlf[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       nq[e] = z2;
       nc[e] = z2;
       no[e] = z2;
+      nlf[e] = z2;
       if (more && rl[e]) {
         if (e >= 1 && e <= E - 2) {
           nq[e] = ld2(cur + (px + 2 * plane + rb[e]) + lo);
           no[e] = ld2(prev + (px + plane + rb[e]) + lo);
+          if (VARC) nlf[e] = ld2(p.lamf + (px + plane + rb[e]) + lo);
         } else {
           nc[e] = ld2(cur + (px + plane + rb[e]) + lo);
         }
@@ -190,8 +203,8 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC
       const double l0 = d2sum_box(c[e].x, m[e].x, q[e].x, ym.x, yp.x, zm, c[e].y, p.ry, p.rz);
       const double l1 = d2sum_box(c[e].y, m[e].y, q[e].y, ym.y, yp.y, c[e].x, zp, p.ry, p.rz);
       const bool keep = xin && ri[e];
-      a[e].x = keep && in0 ? leapfrog(c[e].x, o[e].x, l0, tau2) : 0.0;
-      a[e].y = keep && in1 ? leapfrog(c[e].y, o[e].y, l1, tau2) : 0.0;
+      a[e].x = keep && in0 ? leapfrog(c[e].x, o[e].x, l0, VARC ? lf[e].x : tau2) : 0.0;
+      a[e].y = keep && in1 ? leapfrog(c[e].y, o[e].y, l1, VARC ? lf[e].y : tau2) : 0.0;
       if (e >= 2 && e <= E - 3 && xout && ro[e - 2]) {
         double* dst = p.out1 + (px + rb[e]) + lo;
         if (ok0 && ok1)
@@ -213,8 +226,8 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC
         const double l0 = d2sum_box(ctr.x, w2[e].x, a[e].x, w1[e - 1].x, w1[e + 1].x, zm, ctr.y, p.ry, p.rz);
         const double l1 = d2sum_box(ctr.y, w2[e].y, a[e].y, w1[e - 1].y, w1[e + 1].y, ctr.x, zp, p.ry, p.rz);
         v2d v;
-        v.x = leapfrog(ctr.x, m[e].x, l0, tau2);
-        v.y = leapfrog(ctr.y, m[e].y, l1, tau2);
+        v.x = leapfrog(ctr.x, m[e].x, l0, VARC ? lfp[e].x : tau2);
+        v.y = leapfrog(ctr.y, m[e].y, l1, VARC ? lfp[e].y : tau2);
         if (ro[r]) {
           double* dst = p.out2 + (px - plane + rb[e]) + lo;
           if (ok0 && ok1)
@@ -243,6 +256,8 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(OCC
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       if (e >= 2 && e <= E - 3) w2[e] = w1[e];
+      if (VARC && e >= 2 && e <= E - 3) lfp[e] = lf[e];
+      if (VARC && e >= 1 && e <= E - 2) lf[e] = nlf[e];
       if (e >= 1 && e <= E - 2) {
         w1[e] = a[e];
         m[e] = c[e];
@@ -320,19 +335,19 @@ Plan2 make_plan2(const Layout& l, const LBox& b, const Leapfrog2Tiling& t, i64 s
   return pl;
 }
 
-template <int R, int OCC>
+template <int R, int OCC, bool VARC = false>
 void launch_ro(const Lf2Params& p, int nblocks, bool check, bool nt, hipStream_t st) {
   const dim3 block(64 * kWaves), grid(nblocks);
   if (check) {
     if (nt)
-      hipLaunchKernelGGL((k_leapfrog2_rq<R, true, true, OCC>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog2_rq<R, true, true, OCC, VARC>), grid, block, 0, st, p);
     else
-      hipLaunchKernelGGL((k_leapfrog2_rq<R, true, false, OCC>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog2_rq<R, true, false, OCC, VARC>), grid, block, 0, st, p);
   } else {
     if (nt)
-      hipLaunchKernelGGL((k_leapfrog2_rq<R, false, true, OCC>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog2_rq<R, false, true, OCC, VARC>), grid, block, 0, st, p);
     else
-      hipLaunchKernelGGL((k_leapfrog2_rq<R, false, false, OCC>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog2_rq<R, false, false, OCC, VARC>), grid, block, 0, st, p);
   }
 }
 
@@ -344,7 +359,7 @@ int leapfrog2_partials(const Layout& l, const LBox& box, const Leapfrog2Tiling& 
 
 void launch_leapfrog2(const Layout& l, const Coeffs& c, const double* prev, const double* cur, double* out1,
                       double* out2, const LBox& box, const double* d_s, double ct2, Partial* partials,
-                      const Leapfrog2Tiling& t, hipStream_t stream, i64 sx0, i64 sx1) {
+                      const Leapfrog2Tiling& t, hipStream_t stream, i64 sx0, i64 sx1, const double* lamf) {
   W3D_REQUIRE(prev != out1 && prev != out2 && cur != out1 && cur != out2 && out1 != out2,
               "leapfrog2 needs four distinct buffers");
   if (sx0 > sx1) {  // default: stage 1 real exactly on the updated region of this rank
@@ -370,6 +385,14 @@ void launch_leapfrog2(const Layout& l, const Coeffs& c, const double* prev, cons
   p.rz = c.rz;
   p.ct2 = ct2;
   const bool check = partials != nullptr;
+  p.lamf = lamf ? lamf + kb : nullptr;
+  if (lamf) {  // (a speed field: the VARC instantiations, none built with a register cap — `occupancy` is not consulted)
+    switch (t.rows) {
+      case 1: launch_ro<1, 1, true>(p, pl.nblocks, check, t.nt_store, stream); break;
+      case 2: launch_ro<2, 1, true>(p, pl.nblocks, check, t.nt_store, stream); break;
+      default: launch_ro<4, 1, true>(p, pl.nblocks, check, t.nt_store, stream); break;
+    }
+  } else
   switch (t.rows) {
     case 1: launch_ro<1, 1>(p, pl.nblocks, check, t.nt_store, stream); break;
     case 2:

@@ -132,13 +132,17 @@ struct LfParams {
   double ry, rz;
   // sponge layers (the DAMP instantiations): the six 1-D tables in device memory, global node index −1..N+1
   SpongeView sp;
+  // a speed field (the VARC instantiations): lam·c² per node in the solve layout, offset like cur / out
+  const double* lamf;
   int nbox, ntiles, nblocks, xcd_remap;
   TileBox box[kMaxBoxes];
 };
 
 // DAMP: the damped update of the sponge layers (stencil.hpp leapfrog_damped). gx / rx of the plane are wave-uniform loads
 // issued one plane ahead like sxp; the thread's gy, ry and the gz, rz of its two nodes are loaded once before the march.
-template <int TY, bool CHECK, bool NT, bool DAMP = false>
+// VARC: a speed field — the coefficient of each node comes from LfParams::lamf; the thread's pair is one more 16-byte load
+// per plane, issued one plane ahead with uo's (32 instead of 24 bytes per node). VARC = false keeps its code.
+template <int TY, bool CHECK, bool NT, bool DAMP = false, bool VARC = false>
 __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
   static_assert(TY >= 4, "halo slots need at least 128 + 2*TY threads");
   __shared__ v2d lds[2][TY + 2][kLanes + 2];
@@ -203,13 +207,14 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
   const double* __restrict__ cur = p.cur;
   double* __restrict__ out = p.out;
   const v2d zero2 = {0.0, 0.0};
-  v2d um = zero2, uc = zero2, up = zero2, uo = zero2, hv = zero2;
+  v2d um = zero2, uc = zero2, up = zero2, uo = zero2, hv = zero2, lf = zero2;
   i64 px = (xs + 1) * plane;  // plane base of x
   if (active) {
     um = ld2(cur + px - plane + my);
     uc = ld2(cur + px + my);
     up = ld2(cur + px + plane + my);
     uo = ld2(out + px + my);
+    if (VARC) lf = ld2(p.lamf + px + my);
   }
   if (hr >= 0) hv = ld2(cur + px + hoff);
 
@@ -234,13 +239,14 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
   for (i64 x = xs; x < xe; ++x, px += plane) {
     const int buf = static_cast<int>((x - xs) & 1);
     const bool more = x + 1 < xe;
-    v2d nxt = zero2, uo_n = zero2, hv_n = zero2;
+    v2d nxt = zero2, uo_n = zero2, hv_n = zero2, lf_n = zero2;
     const double nsxp = CHECK && more ? p.s[p.gx0 + x + 1] : 0.0;  // one plane ahead (in-order vmcnt)
     const double ngxp = DAMP && more ? p.sp.gx[p.gx0 + x + 1] : 0.0, nrxp = DAMP && more ? p.sp.rx[p.gx0 + x + 1] : 1.0;
     if (more) {
       if (active) {
         nxt = ld2(cur + px + 2 * plane + my);
         uo_n = ld2(out + px + plane + my);
+        if (VARC) lf_n = ld2(p.lamf + px + plane + my);
       }
       if (hr >= 0) hv_n = ld2(cur + px + plane + hoff);
     }
@@ -255,8 +261,8 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
       const double l0 = d2sum_box(uc.x, um.x, up.x, ym.x, yp.x, zm, uc.y, p.ry, p.rz);
       const double l1 = d2sum_box(uc.y, um.y, up.y, ym.y, yp.y, uc.x, zp, p.ry, p.rz);
       v2d r;
-      r.x = leapfrog(uc.x, uo.x, l0, tau2);
-      r.y = leapfrog(uc.y, uo.y, l1, tau2);
+      r.x = leapfrog(uc.x, uo.x, l0, VARC ? lf.x : tau2);
+      r.y = leapfrog(uc.y, uo.y, l1, VARC ? lf.y : tau2);
       if (DAMP) {
         r.x = leapfrog_damped(r.x, uo.x, fmax(gxp, gyz0), fmin(rxp, ryz0));
         r.y = leapfrog_damped(r.y, uo.y, fmax(gxp, gyz1), fmin(rxp, ryz1));
@@ -287,6 +293,7 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
     up = nxt;
     uo = uo_n;
     hv = hv_n;
+    if (VARC) lf = lf_n;
     sxp = nsxp;
     gxp = ngxp;
     rxp = nrxp;
@@ -322,11 +329,13 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
 // many independent HBM streams stay in flight (R rows × 2 fields × 1 KiB per wave per plane).
 constexpr int kWavesRq = 4;  // waves per workgroup (scheduling only; they do not cooperate)
 
-template <int R, bool CHECK, bool NT, bool DAMP = false>
+// VARC: a speed field — per row the thread's lamf pair, loaded one plane ahead with the row's u^{n−1} pair.
+template <int R, bool CHECK, bool NT, bool DAMP = false, bool VARC = false>
 // (the checked DAMP step with two rows needs 8 VGPRs more than the 128 of four waves per SIMD: it alone builds for fewer
-// waves instead of spilling; every other instantiation keeps its cap)
+// waves instead of spilling; every other instantiation keeps its cap. The VARC steps hold 4·R registers more: with two
+// rows they build for fewer waves too)
 __global__ __launch_bounds__(64 * kWavesRq)
-    __attribute__((amdgpu_waves_per_eu((R <= 2 && !(DAMP && CHECK && R == 2)) ? 4 : 2))) void k_leapfrog_rq(
+    __attribute__((amdgpu_waves_per_eu((R <= 2 && !(DAMP && CHECK && R == 2) && !(VARC && R == 2)) ? 4 : 2))) void k_leapfrog_rq(
     const LfParams p) {
   const int lane = static_cast<int>(threadIdx.x) & 63;
   const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);  // wave-uniform: tile math stays scalar
@@ -375,7 +384,7 @@ __global__ __launch_bounds__(64 * kWavesRq)
   const double* __restrict__ cur = p.cur;
   double* __restrict__ out = p.out;
   const v2d z2 = {0.0, 0.0};
-  v2d m[R], c[R], q[R], o[R];
+  v2d m[R], c[R], q[R], o[R], lf[R];
   double hz[R];
   v2d ht = z2, hb = z2;
   i64 px = (xs + 1) * plane;
@@ -385,6 +394,7 @@ __global__ __launch_bounds__(64 * kWavesRq)
     c[r] = z2;
     q[r] = z2;
     o[r] = z2;
+    lf[r] = z2;
     hz[r] = 0.0;
     if (r < nre) {
       if (act) {
@@ -392,6 +402,7 @@ __global__ __launch_bounds__(64 * kWavesRq)
         c[r] = ld2(cur + px + base + r * pitch);
         q[r] = ld2(cur + px + plane + base + r * pitch);
         o[r] = ld2(out + px + base + r * pitch);
+        if (VARC) lf[r] = ld2(p.lamf + px + base + r * pitch);
       }
       if (hzl || hzr) hz[r] = cur[px + hzoff + r * pitch];
     }
@@ -433,7 +444,7 @@ __global__ __launch_bounds__(64 * kWavesRq)
 
   for (i64 x = xs; x < xe; ++x, px += plane) {
     const bool more = x + 1 < xe;
-    v2d nq[R], no[R];
+    v2d nq[R], no[R], nlf[R];
     double nhz[R];
     v2d nht = z2, nhb = z2;
     const double nsx = CHECK && more ? p.s[p.gx0 + x + 1] : 0.0;
@@ -442,11 +453,13 @@ __global__ __launch_bounds__(64 * kWavesRq)
     for (int r = 0; r < R; ++r) {
       nq[r] = z2;
       no[r] = z2;
+      nlf[r] = z2;
       nhz[r] = 0.0;
       if (more && r < nre) {
         if (act) {
           nq[r] = ld2(cur + px + 2 * plane + base + r * pitch);
           no[r] = ld2(out + px + plane + base + r * pitch);
+          if (VARC) nlf[r] = ld2(p.lamf + px + plane + base + r * pitch);
         }
         if (hzl || hzr) nhz[r] = cur[px + plane + hzoff + r * pitch];
       }
@@ -468,8 +481,8 @@ __global__ __launch_bounds__(64 * kWavesRq)
         const double l0 = d2sum_box(c[r].x, m[r].x, q[r].x, ym.x, yp.x, zm, c[r].y, p.ry, p.rz);
         const double l1 = d2sum_box(c[r].y, m[r].y, q[r].y, ym.y, yp.y, c[r].x, zp, p.ry, p.rz);
         v2d v;
-        v.x = leapfrog(c[r].x, o[r].x, l0, tau2);
-        v.y = leapfrog(c[r].y, o[r].y, l1, tau2);
+        v.x = leapfrog(c[r].x, o[r].x, l0, VARC ? lf[r].x : tau2);
+        v.y = leapfrog(c[r].y, o[r].y, l1, VARC ? lf[r].y : tau2);
         if (DAMP) {
           const double gxy = fmax(gx, gy[r]), rxy = fmin(rx, ry[r]);
           v.x = leapfrog_damped(v.x, o[r].x, fmax(gxy, gz0), fmin(rxy, rz0));
@@ -503,6 +516,7 @@ __global__ __launch_bounds__(64 * kWavesRq)
       c[r] = q[r];
       q[r] = nq[r];
       o[r] = no[r];
+      if (VARC) lf[r] = nlf[r];
       hz[r] = nhz[r];
     }
     ht = nht;
@@ -518,7 +532,7 @@ __global__ __launch_bounds__(64 * kWavesRq)
 }
 
 template <int R>
-void launch_rq(const LfParams& p, int nblocks, bool check, bool nt, bool damp, hipStream_t st);
+void launch_rq(const LfParams& p, int nblocks, bool check, bool nt, bool damp, bool varc, hipStream_t st);
 
 // Host-side tiling plan shared by leapfrog_blocks() and launch_leapfrog().
 struct Plan {
@@ -593,59 +607,73 @@ Plan make_plan(const Layout& l, const LBox* boxes, int nbox, const LeapfrogTilin
   return pl;
 }
 
-template <int TY>
-void launch_lf_ty(const LfParams& p, int nblocks, bool check, bool nt, bool damp, hipStream_t st) {
-  const dim3 block(kLanes, TY), grid(nblocks);
-  if (damp) {  // (sponge layers: the DAMP instantiations; the others are what they were)
-    if (check) {
-      if (nt)
-        hipLaunchKernelGGL((k_leapfrog_lds<TY, true, true, true>), grid, block, 0, st, p);
-      else
-        hipLaunchKernelGGL((k_leapfrog_lds<TY, true, false, true>), grid, block, 0, st, p);
-    } else {
-      if (nt)
-        hipLaunchKernelGGL((k_leapfrog_lds<TY, false, true, true>), grid, block, 0, st, p);
-      else
-        hipLaunchKernelGGL((k_leapfrog_lds<TY, false, false, true>), grid, block, 0, st, p);
-    }
-  } else if (check) {
+// (sponge layers: the DAMP instantiations; a speed field: the VARC ones; the others are what they were)
+template <int TY, bool DAMP, bool VARC>
+void launch_lf_ty_dv(const LfParams& p, const dim3 grid, const dim3 block, bool check, bool nt, hipStream_t st) {
+  if (check) {
     if (nt)
-      hipLaunchKernelGGL((k_leapfrog_lds<TY, true, true>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog_lds<TY, true, true, DAMP, VARC>), grid, block, 0, st, p);
     else
-      hipLaunchKernelGGL((k_leapfrog_lds<TY, true, false>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog_lds<TY, true, false, DAMP, VARC>), grid, block, 0, st, p);
   } else {
     if (nt)
-      hipLaunchKernelGGL((k_leapfrog_lds<TY, false, true>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog_lds<TY, false, true, DAMP, VARC>), grid, block, 0, st, p);
     else
-      hipLaunchKernelGGL((k_leapfrog_lds<TY, false, false>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog_lds<TY, false, false, DAMP, VARC>), grid, block, 0, st, p);
   }
 }
 
-template <int R>
-void launch_rq(const LfParams& p, int nblocks, bool check, bool nt, bool damp, hipStream_t st) {
-  const dim3 block(64 * kWavesRq), grid(nblocks);
-  if (damp) {
-    if (check) {
-      if (nt)
-        hipLaunchKernelGGL((k_leapfrog_rq<R, true, true, true>), grid, block, 0, st, p);
-      else
-        hipLaunchKernelGGL((k_leapfrog_rq<R, true, false, true>), grid, block, 0, st, p);
-    } else {
-      if (nt)
-        hipLaunchKernelGGL((k_leapfrog_rq<R, false, true, true>), grid, block, 0, st, p);
-      else
-        hipLaunchKernelGGL((k_leapfrog_rq<R, false, false, true>), grid, block, 0, st, p);
-    }
-  } else if (check) {
-    if (nt)
-      hipLaunchKernelGGL((k_leapfrog_rq<R, true, true>), grid, block, 0, st, p);
+template <int TY>
+void launch_lf_ty(const LfParams& p, int nblocks, bool check, bool nt, bool damp, bool varc, hipStream_t st) {
+  const dim3 block(kLanes, TY), grid(nblocks);
+  if (varc) {
+    if (damp)
+      launch_lf_ty_dv<TY, true, true>(p, grid, block, check, nt, st);
     else
-      hipLaunchKernelGGL((k_leapfrog_rq<R, true, false>), grid, block, 0, st, p);
+      launch_lf_ty_dv<TY, false, true>(p, grid, block, check, nt, st);
+  } else if (damp) {
+    launch_lf_ty_dv<TY, true, false>(p, grid, block, check, nt, st);
+  } else {
+    launch_lf_ty_dv<TY, false, false>(p, grid, block, check, nt, st);
+  }
+}
+
+template <int R, bool DAMP, bool VARC>
+void launch_rq_dv(const LfParams& p, const dim3 grid, const dim3 block, bool check, bool nt, hipStream_t st) {
+  if (check) {
+    if (nt)
+      hipLaunchKernelGGL((k_leapfrog_rq<R, true, true, DAMP, VARC>), grid, block, 0, st, p);
+    else
+      hipLaunchKernelGGL((k_leapfrog_rq<R, true, false, DAMP, VARC>), grid, block, 0, st, p);
   } else {
     if (nt)
-      hipLaunchKernelGGL((k_leapfrog_rq<R, false, true>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog_rq<R, false, true, DAMP, VARC>), grid, block, 0, st, p);
     else
-      hipLaunchKernelGGL((k_leapfrog_rq<R, false, false>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((k_leapfrog_rq<R, false, false, DAMP, VARC>), grid, block, 0, st, p);
+  }
+}
+
+// VARC is built at R = 1, 2, 4 (8 rows spill already without it) and VARC && DAMP at R = 1, 2: kernels.hpp
+// leapfrog_speed_supported, which launch_leapfrog asks before it comes here.
+template <int R>
+void launch_rq(const LfParams& p, int nblocks, bool check, bool nt, bool damp, bool varc, hipStream_t st) {
+  const dim3 block(64 * kWavesRq), grid(nblocks);
+  if (varc) {
+    if constexpr (R <= 2) {
+      if (damp)
+        launch_rq_dv<R, true, true>(p, grid, block, check, nt, st);
+      else
+        launch_rq_dv<R, false, true>(p, grid, block, check, nt, st);
+    } else if constexpr (R == 4) {
+      if (damp) fail("speed: no damped register-queue step with a speed field at 4 rows per wave");
+      launch_rq_dv<R, false, true>(p, grid, block, check, nt, st);
+    } else {
+      fail("speed: no register-queue step with a speed field at 8 rows per wave");
+    }
+  } else if (damp) {
+    launch_rq_dv<R, true, false>(p, grid, block, check, nt, st);
+  } else {
+    launch_rq_dv<R, false, false>(p, grid, block, check, nt, st);
   }
 }
 
@@ -781,13 +809,20 @@ void launch_init_first(const Layout& l, const Coeffs& c, const double* d_s, doub
   W3D_HIP_CHECK(hipGetLastError());
 }
 
+bool leapfrog_speed_supported(const LeapfrogTiling& t, bool sponge) {
+  if (t.variant != 1) return true;
+  return t.rows == 1 || t.rows == 2 || (t.rows == 4 && !sponge);
+}
+
 int leapfrog_blocks(const Layout& l, const LBox* boxes, int nbox, const LeapfrogTiling& t) {
   return make_plan(l, boxes, nbox, t).npartials;
 }
 
 void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox* boxes, int nbox,
                      const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream,
-                     const SpongeView* sponge) {
+                     const SpongeView* sponge, const double* lamf) {
+  W3D_REQUIRE(!lamf || leapfrog_speed_supported(t, sponge != nullptr),
+              "speed: this single-step tiling has no instantiation with a speed field (8 rows per wave; 4 rows with a sponge)");
   Plan pl = make_plan(l, boxes, nbox, t);
   if (pl.nblocks == 0) return;
   LfParams& p = pl.prm;
@@ -802,20 +837,21 @@ void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double
   p.ry = c.ry;
   p.rz = c.rz;
   p.ct = ct;
-  const bool check = partials != nullptr, damp = sponge != nullptr;
+  const bool check = partials != nullptr, damp = sponge != nullptr, varc = lamf != nullptr;
   if (damp) p.sp = *sponge;
+  p.lamf = varc ? lamf + l.kbase() : nullptr;
   if (t.variant == 1) {
     switch (t.rows) {
-      case 1: launch_rq<1>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
-      case 2: launch_rq<2>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
-      case 4: launch_rq<4>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
-      default: launch_rq<8>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
+      case 1: launch_rq<1>(p, pl.nblocks, check, t.nt_store, damp, varc, stream); break;
+      case 2: launch_rq<2>(p, pl.nblocks, check, t.nt_store, damp, varc, stream); break;
+      case 4: launch_rq<4>(p, pl.nblocks, check, t.nt_store, damp, varc, stream); break;
+      default: launch_rq<8>(p, pl.nblocks, check, t.nt_store, damp, varc, stream); break;
     }
   } else {
     switch (t.ty) {
-      case 4: launch_lf_ty<4>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
-      case 8: launch_lf_ty<8>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
-      default: launch_lf_ty<16>(p, pl.nblocks, check, t.nt_store, damp, stream); break;
+      case 4: launch_lf_ty<4>(p, pl.nblocks, check, t.nt_store, damp, varc, stream); break;
+      case 8: launch_lf_ty<8>(p, pl.nblocks, check, t.nt_store, damp, varc, stream); break;
+      default: launch_lf_ty<16>(p, pl.nblocks, check, t.nt_store, damp, varc, stream); break;
     }
   }
   W3D_HIP_CHECK(hipGetLastError());

@@ -11,7 +11,7 @@
 namespace wave3d {
 
 void write_dump(const std::string& prefix, const Problem& p, const Layout& l, const std::vector<double>& u, int rank,
-                int world, const Dims& d, int step) {
+                int world, const Dims& d, int step, const SpeedRange* speed) {
   if (step < 0) step = p.K;
   const std::string base = world > 1 ? prefix + ".rank" + std::to_string(rank) : prefix;
   std::ofstream f(base + ".bin", std::ios::binary | std::ios::trunc);
@@ -31,6 +31,8 @@ void write_dump(const std::string& prefix, const Problem& p, const Layout& l, co
   // (sponge layers: width, sigma as given (0: the default), face mask; absent without a sponge)
   if (p.sponge.on())
     j << ", \"sponge\": [" << p.sponge.width << ", " << p.sponge.sigma << ", " << p.sponge.faces << "]";
+  // (a speed field: the interior minimum and maximum of c; absent without one)
+  if (speed) j << ", \"speed\": [" << speed->cmin << ", " << speed->cmax << "]";
   j << ", \"tau\": " << p.tau << ", \"step\": " << step << ", \"t\": " << step * p.tau
     << ", \"shape\": [" << l.nx << ", " << l.ny << ", " << l.nz << "], \"offset\": [" << l.gx0 << ", " << l.gy0
     << ", " << l.gz0 << "], \"global_shape\": [" << p.N + 1 << ", " << p.N + 1 << ", " << p.N + 1
@@ -208,6 +210,10 @@ void load_initial(const std::string& prefix, const Problem& p, std::vector<doubl
   psi.clear();
   const bool have = std::ifstream(prefix + ".psi.json").good() || std::ifstream(prefix + ".psi.rank0.json").good();
   if (have) load_dump_global(prefix + ".psi", p, psi, "initial");
+}
+
+void load_speed(const std::string& prefix, const Problem& p, std::vector<double>& c) {
+  load_dump_global(prefix + ".c", p, c, "speed");
 }
 
 }  // namespace wave3d

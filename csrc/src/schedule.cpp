@@ -260,15 +260,17 @@ void plan_msgs(const RankSchedule& s, UnitPlan& u) {
 
 }  // namespace
 
-std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources) {
+std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources, SpeedPlan speed) {
   std::vector<UnitPlan> units;
   const int K = s.prob.K;
   int n = start_n;
-  if ((s.mode == Mode::kFusedSingle && s.opt.tb) || s.mode == Mode::kDeepTb) {
+  const bool varc = speed != SpeedPlan::kNone;
+  W3D_REQUIRE(!varc || (s.world == 1 && !analytic), "speed: one rank and a stored start only");
+  if (((s.mode == Mode::kFusedSingle && s.opt.tb) || s.mode == Mode::kDeepTb) && !varc) {
     plan_passes(s, n, analytic, units);
   } else if (s.mode == Mode::kFusedSingle) {
     while (n <= K - 1) {
-      const bool f = n + 2 <= K && !s.is_check(n + 1);
+      const bool f = n + 2 <= K && !s.is_check(n + 1) && speed != SpeedPlan::kSingles;
       units.push_back(UnitPlan{n, f ? 2 : 1});
       n += f ? 2 : 1;
     }
@@ -299,7 +301,7 @@ std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analyt
   // the next solve's first exchange, and those can be the last unit's inputs, which a rebuild reads again.)
   // (Nor with point sources: the source correction is added to the stored u^K after the pass, and a rebuild runs the
   // pass again over it.)
-  if (nu > 0 && !sources && !s.opt.keep_prev && s.nbuf == 4 && !s.push && !(s.sdma && s.opt.poison_ghosts) &&
+  if (nu > 0 && !sources && !varc && !s.opt.keep_prev && s.nbuf == 4 && !s.push && !(s.sdma && s.opt.poison_ghosts) &&
       ((s.mode == Mode::kFusedSingle && s.opt.tb) || tb)) {
     UnitPlan& u = units.back();
     u.drop_prev = u.fused() && !u.exchange && runs_p2(s, u.steps, u.analytic);
@@ -364,13 +366,15 @@ std::vector<LinkPlan> plan_links(const RankSchedule& s) {
   return v;
 }
 
-Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool init_kernel) {
+Traffic traffic(const RankSchedule& s, const std::vector<UnitPlan>& units, bool init_kernel, bool speed) {
   Traffic t;
   const Layout& l = s.lay;
   const double plane_bytes = static_cast<double>(l.plane) * sizeof(double);
   const double node_bytes = static_cast<double>(l.cx1 - l.cx0) * static_cast<double>(l.cy1 - l.cy0) *
                             static_cast<double>(l.cz1 - l.cz0) * sizeof(double);
   if (init_kernel) t.field_bytes += 2.0 * node_bytes;  // init kernel: u¹, u² (or u⁰, u¹)
+  // (a speed field: the first-step kernel and every unit read lamf once)
+  if (speed) t.field_bytes += node_bytes * static_cast<double>(units.size() + (init_kernel ? 1 : 0));
   for (const UnitPlan& u : units) {
     t.field_bytes += node_bytes * (u.analytic ? 2.0 : u.fused() ? 4.0 : 3.0);
     // (the stored u^{n+S−1} ghost planes: one plane per face)

@@ -57,6 +57,7 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
   size_t free_b = 0, total_b = 0;
   W3D_HIP(hipMemGetInfo(&free_b, &total_b));
   sch_ = make_rank_schedule(prob, o, rank, world, static_cast<double>(free_b));
+  temporal_asked_ = o.temporal;
 
   // device memory
   int ncu = 0;
@@ -175,6 +176,61 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
   }
 }
 
+void GpuSolver::set_speed(const double* c, bool force) {
+  DeviceScope scope(dev_, true);
+  if (!c) {
+    if (!speed()) return;
+    W3D_HIP(hipDeviceSynchronize());
+    drop_graphs();
+    W3D_HIP(hipFree(lamf_dev_));
+    lamf_dev_ = nullptr;
+    speed_range_ = SpeedRange{};
+    if (speed_eig_) {
+      W3D_HIP(hipFree(init_[0]));
+      init_[0] = nullptr;
+      speed_eig_ = false;
+    }
+    return;
+  }
+  W3D_REQUIRE(sch_.world == 1 && !loopback_, "speed: one GPU rank that spans the domain only (no GpuGroup, RCCL ranks, --np, "
+                                             "runtime=\"process\" or multi-device group)");
+  W3D_REQUIRE(!sch_.opt.fake_comm, "speed: not on a fake rank");
+  W3D_REQUIRE(!sch_.push && !sch_.sdma && !sch_.opt.push && !sch_.opt.sdma, "speed: not on the push or copy-engine transports");
+  W3D_REQUIRE(!(sch_.opt.tiling.variant == 1 && sch_.opt.tiling.rows == 8),
+              "speed: the register-queue single step with 8 rows per wave has no form with a speed field (it spills "
+              "already without one); use 1, 2 or 4 rows");
+  W3D_REQUIRE(leapfrog_speed_supported(sch_.opt.tiling, sponge()),
+              "speed: with a sponge the register-queue single step is built for 1 or 2 rows per wave only");
+  W3D_REQUIRE(resume_n_ == 0, "speed: not together with set_state / --resume");
+  W3D_REQUIRE(temporal_asked_ <= 2 || temporal_asked_ == SolverOptions{}.temporal,
+              "speed: temporal = " + std::to_string(temporal_asked_) + " asks for fused passes of more than two steps, which "
+              "have no coefficient form; use temporal = 1 or 2 (the default runs two-step pairs)");
+  std::vector<double> host(static_cast<size_t>(sch_.lay.total));
+  const SpeedRange r = speed_to_local(sch_.prob, sch_.lay, c, host.data(), nullptr);
+  speed_cfl(sch_.prob, r, force);
+  const size_t bytes = static_cast<size_t>(sch_.lay.bytes());
+  const Layout il = initial_layout(sch_.prob, sch_.lay);
+  if (!lamf_dev_) {  // (the memory planner's view: the fifth field buffer — and the eigenmode array — must fit what is free)
+    size_t free_b = 0, total_b = 0;
+    W3D_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t need = bytes + (initial_ ? 0u : static_cast<size_t>(il.bytes()));
+    W3D_REQUIRE(static_cast<double>(need) <= 0.9 * static_cast<double>(free_b),
+                "speed: the coefficient field (" + std::to_string(need >> 20) + " MiB) does not fit into free device memory");
+  }
+  W3D_HIP(hipDeviceSynchronize());
+  drop_graphs();
+  if (!lamf_dev_) W3D_HIP(hipMalloc(&lamf_dev_, bytes));
+  W3D_HIP(hipMemcpy(lamf_dev_, host.data(), bytes, hipMemcpyHostToDevice));
+  speed_range_ = r;
+  if (!initial_ && !speed_eig_) {  // no set_initial: the eigenmode array through the first-step-field path
+    init_lay_ = il;
+    const std::vector<double> phi0 = eigenmode_local(sch_.prob, il);
+    W3D_HIP(hipMalloc(&init_[0], static_cast<size_t>(il.bytes())));
+    W3D_HIP(hipMemcpy(init_[0], phi0.data(), static_cast<size_t>(il.bytes()), hipMemcpyHostToDevice));
+    speed_eig_ = true;
+  }
+}
+
 void GpuSolver::sponge_check_nodes(const i64* ijk, int n, const char* what) const {
   if (!sponge()) return;
   const Sponge& sp = sch_.prob.sponge;
@@ -217,7 +273,7 @@ GpuSolver::~GpuSolver() {
   for (BoxCopyTable& t : pack_tab_) free_box_copy_table(t);
   for (BoxCopyTable& t : unpack_tab_) free_box_copy_table(t);
   if (pk_dev_) (void)hipFree(pk_dev_);
-  for (double* p : {u_[0], u_[1], u_[2], u_[3], d_s_, send_buf_, recv_buf_, init_[0], init_[1], sponge_dev_})
+  for (double* p : {u_[0], u_[1], u_[2], u_[3], d_s_, send_buf_, recv_buf_, init_[0], init_[1], sponge_dev_, lamf_dev_})
     if (p) (void)hipFree(p);
   if (energy_part_) (void)hipFree(energy_part_);
   if (recv_dev_) (void)hipFree(recv_dev_);
@@ -247,7 +303,7 @@ GpuSolver::~GpuSolver() {
 }
 
 size_t GpuSolver::device_bytes() const {
-  return static_cast<size_t>(sch_.nbuf) * static_cast<size_t>(sch_.lay.bytes()) +
+  return static_cast<size_t>(sch_.nbuf + (speed() ? 1 : 0)) * static_cast<size_t>(sch_.lay.bytes()) +
          recv_bytes_ + send_bytes_ + static_cast<size_t>(n_partials_) * sizeof(Partial) +
          static_cast<size_t>(sch_.prob.N + 3) * sizeof(double) * (sponge() ? 7u : 1u) + tb_bytes_ +
          ((init_[0] ? 1u : 0u) + (init_[1] ? 1u : 0u)) * static_cast<size_t>(init_lay_.bytes()) +
@@ -291,6 +347,7 @@ void GpuSolver::set_initial(const double* phi, const double* psi) {
     W3D_HIP(hipMemcpy(init_[k], host.data(), bytes, hipMemcpyHostToDevice));
   }
   if (sch_.world == 1) energy_alloc();
+  speed_eig_ = false;  // (init_[0] is the caller's φ now)
   initial_ = true;
   initial_runs_ = 0;
   resume_n_ = 0;
@@ -397,6 +454,7 @@ void GpuSolver::source_correct(const UnitPlan* u, double* prev, double* last) {
 Partial GpuSolver::energy_sums(int which) const {
   W3D_REQUIRE(sch_.world == 1, "energy: one rank only (multi-rank: Solver.energy assembles the global fields)");
   W3D_REQUIRE(which == 0 || which == 1, "energy: which is 0 (E at K-1/2) or 1 (E at 1/2)");
+  W3D_REQUIRE(!speed(), "speed: k_energy has no mass weight 1/c^2; Solver.energy downloads both levels and runs cpu_energy");
   W3D_REQUIRE(runs_ > 0 && (!initial_ || initial_runs_ > 0), "energy: no solve has run yet");
   W3D_REQUIRE(which == 0 || initial_, "energy: E(1/2) is kept by solves that start from set_initial");
   DeviceScope scope(dev_, true);
@@ -422,6 +480,7 @@ void GpuSolver::set_state(const double* prev, const double* cur, int n0) {
   W3D_REQUIRE(sch_.mode != Mode::kDeepTb || sch_.prob.K - n0 >= 2, "resume: the multi-rank LDS passes need >= 2 steps left");
   W3D_REQUIRE(sch_.mode != Mode::kDeep || (sch_.prob.K - n0) % 2 == 0, "resume: two-step passes need an even step count left");
   W3D_REQUIRE(n_src_ == 0, "sources: not together with set_state (a resumed solve has no step 0 to start the wavelet from)");
+  W3D_REQUIRE(!speed(), "speed: not together with set_state / --resume");
   if (initial_) {  // (the two starts replace each other)
     W3D_HIP(hipDeviceSynchronize());
     for (double*& p : init_) {
@@ -483,7 +542,7 @@ void GpuSolver::phase_init() {
     W3D_HIP(hipMemsetAsync(trace_, 0xFF, static_cast<size_t>(K + 1) * recv_.size() * sizeof(double), s0_));
   // one rank on the LDS kernel: the first pass starts from the analytic u⁰, u¹ itself (no init kernel, no reads)
   analytic_ = (sch_.mode == Mode::kFusedSingle || sch_.mode == Mode::kDeepTb) && sch_.analytic_ok() && resume_n_ == 0 &&
-              !initial_ && !recording_ && n_src_ == 0 && !sponge();  // (receivers: both start levels are stored, rows 0
+              !initial_ && !recording_ && n_src_ == 0 && !sponge() && !speed();  // (receivers: both start levels are stored, rows 0
                                                         // and 1 are gathered; sources: u¹ is corrected in memory;
                                                         // sponge layers: the start is stored, as with receivers)
   if (resume_n_ > 0) {  // loaded state: u^{n0−1} → buf 0, u^{n0} → buf 1 (ghosts included)
@@ -493,12 +552,13 @@ void GpuSolver::phase_init() {
       W3D_HIP(hipMemcpyAsync(u_[1], resume_[1].data(), bytes, hipMemcpyHostToDevice, s0_));
     });
     start_n_ = resume_n_;
-  } else if (initial_) {  // user-supplied φ, ψ: u⁰ → buf 0, u¹ → buf 1 (ghosts included) from the device-resident copies
+  } else if (initial_ || speed()) {  // user-supplied φ, ψ: u⁰ → buf 0, u¹ → buf 1 (ghosts included) from the device-resident copies
+    // (a speed field without set_initial: init_[0] is the eigenmode array, init_[1] null; the coefficient per node)
     timed(kPhaseInit, s0_, [&] {
-      launch_first_step_field(sch_.lay, init_lay_, coef_, sch_.prob.tau, init_[0], init_[1], u_[0], u_[1], s0_);
+      launch_first_step_field(sch_.lay, init_lay_, coef_, sch_.prob.tau, init_[0], init_[1], u_[0], u_[1], s0_, lamf_dev_);
     });
     timed(kPhaseCheck, s0_, [&] {
-      if (energy_part_ && sch_.world == 1) {  // E^{1/2}, kept in its device slot
+      if (energy_part_ && sch_.world == 1 && !speed()) {  // E^{1/2}, kept in its device slot
         const int ne = energy_partials(sch_.lay);
         launch_energy(sch_.lay, coef_, sch_.prob.tau, u_[0], u_[1], energy_part_, s0_);
         launch_energy_reduce(energy_part_, ne, energy_part_ + ne + 1, s0_);
@@ -534,7 +594,7 @@ void GpuSolver::phase_init() {
   cur_ = 1;
   old_ = 0;
   // (sponge layers: like sources, the last pass keeps both levels — a rebuild would need the slabs' recomputation too)
-  units_ = plan_units(sch_, start_n_, analytic_, n_src_ > 0 || sponge());
+  units_ = plan_units(sch_, start_n_, analytic_, n_src_ > 0 || sponge(), speed_plan());
   if (sch_.push) push_upload();
 }
 
@@ -766,7 +826,7 @@ void GpuSolver::unit_interior(int i) {
       });
     }
     np = off + n_dint_;
-  } else if ((sch_.mode == Mode::kFusedSingle && sch_.opt.tb && u.fused()) || sch_.mode == Mode::kDeepTb) {
+  } else if ((sch_.mode == Mode::kFusedSingle && sch_.opt.tb && u.fused() && !speed()) || sch_.mode == Mode::kDeepTb) {
     // S steps in one LDS pass (on slab ranks: the interior left between this unit's shells); every checked level
     // has its own block of partials
     if (sch_.mode != Mode::kDeepTb) tb_slots_ = 0;
@@ -790,10 +850,10 @@ void GpuSolver::unit_interior(int i) {
     timed(kPhaseCompute, s0_, [&] {
       if (u.fused())
         launch_leapfrog2(sch_.lay, coef_, u_[old_], u_[cur_], u_[uf_[0]], u_[uf_[1]], sch_.full, s, ct,
-                         chk ? partials_ : nullptr, sch_.opt.tiling2, s0_);
+                         chk ? partials_ : nullptr, sch_.opt.tiling2, s0_, 1, 0, lamf_dev_);
       else
         launch_leapfrog(sch_.lay, coef_, u_[cur_], u_[old_], &sch_.full, 1, s, ct, chk ? partials_ : nullptr, sch_.opt.tiling,
-                        s0_, sponge_arg());
+                        s0_, sponge_arg(), lamf_dev_);
     });
     np = u.fused() ? n_fused_ : n_full_;
   } else if (sch_.split()) {
@@ -805,7 +865,7 @@ void GpuSolver::unit_interior(int i) {
   } else {
     timed(kPhaseCompute, s0_, [&] {
       launch_leapfrog(sch_.lay, coef_, u_[cur_], u_[old_], &sch_.full, 1, s, ct, chk ? partials_ : nullptr, sch_.opt.tiling,
-                      s0_, sponge_arg());
+                      s0_, sponge_arg(), lamf_dev_);
     });
     np = n_full_;
   }

@@ -66,6 +66,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="absorbing sponge layers of W nodes next to the faces FACES, a subset of the letters xXyYzZ (lower "
                          "case: the low face; default all six), peak damping rate SIGMA (default 3 ln(1000) / (2 W h)); "
                          "one rank, backends hip and cpu; the error lines then have no meaning")
+    ap.add_argument("--speed", default="", metavar="PREFIX",
+                    help="variable wave speed: solve u_tt = c(x)^2 Lap u with c from the dump PREFIX.c (the --initial "
+                         "format; face values ignored, interior values finite and > 0; courant * max c <= 1 unless "
+                         "--force); one rank, backends hip (temporal 1 or 2) and cpu; not with --resume; the error lines "
+                         "then have no meaning")
     ap.add_argument("--force", action="store_true", help="run even if the CFL condition is violated")
     ap.add_argument("--quiet", action="store_true")
     return ap
@@ -93,6 +98,8 @@ def main(argv=None) -> int:
         ap.error("--energy needs --initial (E(1/2) is kept by solves that start from it)")
     if a.sources and a.resume:
         ap.error("--sources and --resume exclude each other")
+    if a.speed and a.resume:
+        ap.error("speed: not together with --resume")
     if bool(a.receivers) != bool(a.traces):
         ap.error("--receivers FILE and --traces OUT go together")
     sponge = None
@@ -158,6 +165,18 @@ def main(argv=None) -> int:
                       f"{list(spec.edges)}", file=sys.stderr)
                 return 2
         s.set_state(prev, cur, int(meta_c["step"]))
+    speed_range = None
+    if a.speed:
+        c, m = dumpio.load(a.speed + ".c")
+        for key, want in (("N", a.N), ("tau", a.tau), ("L", a.L)):  # (the checks --initial makes)
+            got = m.get(key)
+            if got is None or not math.isclose(float(got), float(want), rel_tol=1e-15, abs_tol=0.0):
+                print(f"wave3d: speed: dump {key} = {got} differs from the run's {want}", file=sys.stderr)
+                return 2
+        s.set_speed(c, a.force)
+        speed_range = [float(v) for v in s.native.speed_range]
+        print("wave3d: a speed field is set: the error columns compare with the constant-speed eigenmode and have no "
+              "meaning", file=sys.stderr)
     if a.initial:
         fields = []
         for part in ("phi", "psi"):
@@ -232,11 +251,14 @@ def main(argv=None) -> int:
                            **({"energy_start": e_start, "energy_end": e_end} if a.energy else {}),
                            **({"sources": n_sources} if a.sources else {}),
                            **({"sponge": list(spec.sponge)} if spec.sponge is not None else {}),
+                           **({"speed": speed_range} if speed_range is not None else {}),
                            "steps": [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]}, f)
     if a.traces:
         dumpio.save_traces(a.traces, s.traces().numpy(), nodes, N=a.N, K=a.K, L=a.L, tau=a.tau, box=spec.edges)
     if a.dump or a.checkpoint:
         sponge_meta = {"sponge": list(spec.sponge)} if spec.sponge is not None else None  # (absent without a sponge)
+        if speed_range is not None:  # (... and a speed field only when set: the interior minimum and maximum of c)
+            sponge_meta = {**(sponge_meta or {}), "speed": speed_range}
 
         def write(prefix, which):
             if s.transport in ("loopback", "rccl-self", "push", "sdma"):

@@ -100,7 +100,7 @@ class Solver:
                  tb_min_planes: int | None = None, rccl: bool = True, autotune: bool = False,
                  autotune_rounds: int = 5, copy_engines: bool = False, fused_pack: bool = True,
                  ghost_store: bool = True, keep_prev: bool = False,
-                 runtime: str = "inproc", sponge=None):
+                 runtime: str = "inproc", sponge=None, speed=None):
         import dataclasses
 
         import torch.distributed as dist
@@ -133,6 +133,24 @@ class Solver:
             if not tb and temporal >= 2:
                 raise ValueError("sponge: tb=False runs k_leapfrog2 pairs, which have no damped form; use the LDS "
                                  "passes or temporal=1")
+        self._speed = None  # (set_speed's global c: the hip backend's weighted energy is computed from it on the host)
+        self._force = bool(force)
+        if speed is not None:
+            # speed = a global (N+1)³ array c(x): u_tt = c²Δu. One native rank: CpuSolver is the definition, one GpuSolver
+            # that spans the domain matches it; nothing else reads a coefficient per node
+            if runtime == "process":
+                raise ValueError("speed: not with runtime='process' (one in-process rank only)")
+            if world > 1:
+                raise ValueError("speed: one rank only (a world larger than 1 of any kind is not supported)")
+            if self.backend == "torch" or self.transport == "torch":
+                raise ValueError("speed: the native backends only (backend 'hip' with transport 'rccl', or 'cpu')")
+            if self.transport in ("push", "push-ipc", "sdma", "sdma-ipc", "loopback", "rccl-self", "multi-device") \
+                    or copy_engines:
+                raise ValueError("speed: one GPU rank that spans the domain only (no group, push or copy-engine "
+                                 "transport)")
+            if temporal in (3, 4):
+                raise ValueError(f"speed: temporal={temporal} asks for fused passes of more than two steps, which have "
+                                 "no coefficient form; use temporal=1 or 2 (the default runs two-step pairs)")
         self._impl = None
         self._initial = None  # (set_initial's global phi, psi: a group's E(1/2) is computed from them on the host)
         if runtime not in ("inproc", "process"):
@@ -237,6 +255,8 @@ class Solver:
             self.dims = (1, 1, 1)
         else:
             self.dims = (1, 1, 1)
+        if speed is not None:
+            self.set_speed(speed)
 
     def _init_process(self, device, decomp, temporal, overlap, graph, rccl, autotune, group, flags=()) -> None:
         """runtime="process": this rank's production solver in a ``bin/wave3d --serve`` child (graph-captured under
@@ -374,6 +394,29 @@ class Solver:
                                                 dtype=np.float64).reshape(-1))
         self._impl.set_state(to_np(prev), to_np(cur), int(step))
 
+    def set_speed(self, c, force: bool | None = None) -> None:
+        """Variable wave speed: every following run() solves u_tt = c(x)²·Δu with ``c`` a GLOBAL (N+1)³ float64 array
+        or tensor (face values ignored; interior values finite and > 0; courant·max c ≤ 1 unless ``force``, default
+        the constructor's). ``None`` clears it. ``CpuSolver`` is the definition; one HIP rank that spans the domain
+        matches it bit for bit on single steps and two-step pairs (``temporal`` 1, 2 or the default). The error
+        columns then mean nothing; ``energy`` carries the mass weight 1/c². Not with ``set_state``."""
+        import numpy as np
+
+        if self.runtime == "process":
+            raise ValueError("speed: not with runtime='process' (use bin/wave3d --speed)")
+        if self.backend == "torch" or self.transport == "torch" or not hasattr(self._impl, "set_speed"):
+            raise ValueError("speed: one native rank only (backend 'hip' on one GPU rank, or 'cpu')")
+        if c is None:
+            self._impl.set_speed(None)
+            self._speed = None
+            return
+        n = self.spec.N + 1
+        a = np.ascontiguousarray(c.cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float64)
+        if a.size != n * n * n:
+            raise ValueError(f"speed: expected a global ({n}, {n}, {n}) field, got shape {a.shape}")
+        self._impl.set_speed(a.reshape(-1), self._force if force is None else bool(force))
+        self._speed = a.reshape(-1)
+
     def set_initial(self, phi, psi=None) -> None:
         """Solve from user-supplied initial data: ``phi`` = u(·,0) and optional ``psi`` = u_t(·,0) (None: 0), GLOBAL
         (N+1)³ float64 arrays or tensors as ``set_state`` takes its fields. Values on the six faces are ignored (u⁰
@@ -503,6 +546,23 @@ class Solver:
         if self.backend == "torch" or self.transport == "torch":
             raise ValueError("energy needs the native hip or cpu backend")
         C = load()
+        if self._speed is not None and self.backend == "hip":
+            # a speed field on the hip backend: both levels on the host, cpu_energy with the mass weight 1/c² (k_energy
+            # has none) — the path a group takes below
+            prob = self.spec.native()
+            lay = C.make_layout(prob, C.rank_box(prob, C.Dims(1, 1, 1), 0))
+            lamf, c2, _, _ = C.speed_to_local(prob, lay, self._speed)
+            if which == 0:
+                a, b = (C.initial_to_local(lay, np.ascontiguousarray(self.global_field(w).numpy()).reshape(-1))
+                        for w in (1, 0))
+            else:
+                src = C.initial_layout(prob, lay)
+                init = self._initial
+                phi = C.eigenmode_local(prob, src) if init is None else C.initial_to_local(src, init[0])
+                psi = None if init is None or init[1] is None else C.initial_to_local(src, init[1])
+                a, b = np.zeros(lay.total), np.zeros(lay.total)
+                C.cpu_first_step_field(lay, src, C.Coeffs.from_problem(prob), self.spec.tau, phi, psi, a, b, lamf)
+            return float(C.cpu_energy(prob, lay, a, b, c2)["E"])
         if not isinstance(self._impl, C.GpuGroup) and self.world == 1:
             return float(self._impl.energy(int(which)))
         if not isinstance(self._impl, C.GpuGroup):

@@ -121,7 +121,8 @@ constexpr Personality kPersonalities[] = {
                "                     (default 3 ln(1000) / (2 W h)). One GPU rank or --cpu. The error lines then have no meaning\n"
                "  --speed P          variable wave speed: solve u_tt = c(x)^2 Lap u with c from the dump P.c (the --initial\n"
                "                     format; face values ignored, interior values finite and > 0; courant * max c <= 1 unless\n"
-               "                     --force). One GPU rank (single steps and two-step pairs; --temporal 1 or 2) or --cpu;\n"
+               "                     --force). One GPU rank (fused passes of up to 4 steps; --temporal 1 or 2 / --no-tb: single\n"
+               "                     steps and two-step pairs; --temporal 3 or 4 refused; with receivers, sources or a sponge: single steps) or --cpu;\n"
                "                     not with --resume. The error lines then have no meaning\n"
                "  --force            run even if the CFL condition is violated\n"
                "  --quiet            only the summary\n");

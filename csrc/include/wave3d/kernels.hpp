@@ -205,6 +205,11 @@ struct PassArgs {
   // the pass starts at n = 1 from u⁰ = φ and u¹ computed in the kernel (init_first's formulas, bit-identical): prev /
   // cur are not read, it writes u^S, u^{S+1} with no HBM reads
   bool analytic_start = false;
+  // a speed field (cpu.hpp speed_to_local; device array in layout `l`): the pair-tiled pass's VARC instantiations,
+  // S = 2..kP2VarcMaxStages — every stage takes lamf[p] of its own node, 40/S instead of 32/S bytes per node-step,
+  // bit-identical to S cpu_leapfrog steps with the same array. Refused ("speed: ...") with analytic_start, out1 = nullptr,
+  // push or pack, and wherever the launch would not run on the pair-tiled kernel.
+  const double* lamf = nullptr;
   // slab peer-push transport and fused z-face pack (k_leapfrog_tb only): the host copy, which the launcher reads, and
   // the same entry in device memory, which the kernel reads
   const TbPush *push = nullptr, *push_dev = nullptr;
@@ -215,6 +220,14 @@ struct PassArgs {
 // plan set p.nblocks: buffers from the plane the x ghosts start at, coefficients, check mask and partials,
 // the grid padded to grid_blocks (xper stays the active blocks' per-XCD share: else the remap would hand every tile to
 // the first XCDs — measured: a slab rank's 256 tiles on 4 of 8 XCDs, passes 2.2x slower). false: nothing to launch.
+// (p.lamf where the parameters have one — P2Params; k_leapfrog_tb has no coefficient form and its launcher refuses one)
+template <class Params>
+auto set_pass_lamf(Params& p, const double* v, int) -> decltype(p.lamf = v, void()) {
+  p.lamf = v;
+}
+template <class Params>
+void set_pass_lamf(Params&, const double*, long) {}
+
 template <class Params>
 bool fill_pass_params(Params& p, const Layout& l, const Coeffs& c, const PassArgs& a, const char* name) {
   W3D_REQUIRE(a.out1 != a.out2 && (a.analytic_start || (a.prev != a.out1 && a.prev != a.out2 && a.cur != a.out1 &&
@@ -232,6 +245,7 @@ bool fill_pass_params(Params& p, const Layout& l, const Coeffs& c, const PassArg
   p.cur = a.analytic_start ? nullptr : a.cur + kb;
   p.out1 = a.out1 != nullptr ? a.out1 + kb : nullptr;
   p.out2 = a.out2 + kb;
+  set_pass_lamf(p, a.lamf != nullptr ? a.lamf + kb : nullptr, 0);
   p.s = a.d_s;
   p.tau2 = c.lam;  // τ²/h² and τ²/(2h²): the coefficients of d2sum
   p.half_tau2 = c.half_lam;

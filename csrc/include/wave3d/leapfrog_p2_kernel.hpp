@@ -267,6 +267,7 @@ struct P2Params {
   double tau2, half_tau2;
   double ct[5];
   double ry, rz;  // rectangular box (BOX instantiations): h_x²/h_y², h_x²/h_z² (stencil.hpp::d2sum_box)
+  const double* lamf;  // a speed field (VARC instantiations): lam·c² per node, x base as prev / cur (else nullptr)
 #ifdef W3D_EXPERIMENT_WGTIME
   unsigned long long* wgtime;  // (perf study) 4 wall-clock stamps per workgroup, pinned host memory
 #endif
@@ -358,8 +359,17 @@ __device__ __forceinline__ int p2_desc(int tid) {
 // BOX: a rectangular box — every Laplacian is d2sum_box with the ratios p.ry, p.rz (wave-uniform kernel arguments:
 // scalar operands of two v_fma_f64 that replace two v_add_f64, no vector register more). Cube problems launch the
 // BOX = false instantiations, whose code is what it was before the flag existed.
-template <int S, int CM, bool INIT, bool CH, bool BOX = false>
+// VARC: a speed field (load passes only) — the coefficient of a node is its own lamf value (cpu.hpp speed_to_local),
+// stage k at plane i − (k−1) takes the pair's lamf of that plane. The region waves load the pair of plane i+1 with the
+// pair's own offset right after the u^n load of iteration i (the ring waves through a zero-size descriptor, like
+// u^{n−1}: every wave still issues one vector-memory sequence), into a register queue lq of four planes at slot
+// (x − i0) & 3 like the levels'. Stage 1 of a plane replaces the loaded pair by its Dirichlet-masked value (a node
+// outside the global interior: 0, whatever the array holds there — the constant passes' lam_lo / lam_hi), stages 2 and 3
+// read the slot; the plane that the new load overwrites (i − 3) moves to lqo[0] for stage 4 first, and lqo[0] to lqo[1]
+// for stage 5: 4 registers per plane, S + 1 planes, where lam_lo / lam_hi took 4. VARC = false keeps its code.
+template <int S, int CM, bool INIT, bool CH, bool BOX = false, bool VARC = false>
 __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
+  static_assert(!(VARC && INIT), "p2: a speed solve has a stored start, no analytic-start pass");
   using G = Geo<S>;
   constexpr int E = G::E, R0 = G::R0, R1 = G::R1;
   // late loads (S ≥ 4): u^n plane i+2 right after the commit (into plane i−2's dead slot), u^{n−1} plane i+1 after
@@ -535,12 +545,15 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
     // are read, so their latency and the tables' overlap instead of following each other (the prologue took ≈ 4 µs per
     // pass and workgroup, profiles/r6/wgtime/)
     D2 pq[4] = {D2m(0.0, 0.0), D2m(0.0, 0.0), D2m(0.0, 0.0), D2m(0.0, 0.0)};
+    D2 pql = D2m(0.0, 0.0);  // (VARC: lamf plane i0)
+    (void)pql;
     if constexpr (!INIT) {
       const int x0p = wx0 - S + 1;  // (= i0 below)
       pq[0] = load_pair(std::false_type{}, p.cur, x0p - 1);
       pq[1] = load_pair(std::false_type{}, p.cur, x0p);
       pq[2] = load_pair(std::false_type{}, p.cur, x0p + 1);
       pq[3] = load_pair(std::false_type{}, p.prev, x0p);
+      if constexpr (VARC) pql = load_pair(std::false_type{}, p.lamf, x0p);
     }
     {
       auto sc = [&](int g) __attribute__((always_inline)) { return p.s[g < -1 ? -1 : g > N + 1 ? N + 1 : g]; };
@@ -582,6 +595,13 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
     D2 Lm[2] = {D2m(0.0, 0.0), D2m(0.0, 0.0)};
     D2 phq[2] = {D2m(0.0, 0.0), D2m(0.0, 0.0)};  // (analytic start: the pair's own φ by plane parity)
     (void)phq;
+    // (VARC) the coefficient queue: planes i−2..i+1 by slot, and the planes i−3, i−4 of stages 4 and 5
+    constexpr int kNLqo = S > 4 ? S - 3 : 1;
+    D2 lq[4] = {D2m(0.0, 0.0), D2m(0.0, 0.0), D2m(0.0, 0.0), D2m(0.0, 0.0)};
+    D2 lqo[kNLqo];
+    static_for<0, kNLqo>([&](auto ic) __attribute__((always_inline)) { lqo[decltype(ic)::value] = D2m(0.0, 0.0); });
+    (void)lq;
+    (void)lqo;
 
     const int i0 = wx0 - S + 1, i1 = wx1 + S - 2 + (kSplitSt && o1x1 > wx1 ? 1 : 0);
     // out1 == nullptr: level S−1 is not stored (the last pass of a solve, whose u^{K−1} nothing may ever read). A
@@ -618,6 +638,13 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
       const bool xown = BK || (xp >= wx0 && xp < wx1);
       const bool xown1 = BK || (xp >= o1x0 && xp < o1x1);  // (stores of level S−1; bulk planes are inside the box)
       D2 v = D2m(0.0, 0.0);
+      D2 lm = D2m(lam_lo, lam_hi);
+      if constexpr (VARC) {
+        // (stage 1 masks the plane's loaded pair once, for every later stage; unconditional like the level queues'
+        // writes below)
+        if constexpr (k == 1) lq[s0] = D2m(rl ? lq[s0].x : 0.0, rh ? lq[s0].y : 0.0);
+        lm = k <= 3 ? lq[s0] : lqo[k > 3 ? k - 4 : 0];
+      }
       if (inr && wst >= k) {  // (wave-uniform)
         const D2 c = L[k - 1][s0], xm = L[k - 1][sm], xq = L[k - 1][sp];
         D2 ym, yp;
@@ -638,7 +665,7 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
         const double lapl = d2sum_t<BOX>(c.x, xm.x, xq.x, ym.x, yp.x, zm, c.y, p.ry, p.rz);
         const double laph = d2sum_t<BOX>(c.y, xm.y, xq.y, ym.y, yp.y, c.x, zq, p.ry, p.rz);
         const D2 o = k == 1 ? Lm[kLate ? 0 : (D & 1)] : L[k > 1 ? k - 2 : 0][s0];
-        v = D2m(leapfrog(c.x, o.x, lapl, lam_lo), leapfrog(c.y, o.y, laph, lam_hi));
+        v = D2m(leapfrog(c.x, o.x, lapl, lm.x), leapfrog(c.y, o.y, laph, lm.y));
         if constexpr (!BK) {
           if (!xreal(xp)) v = D2m(0.0, 0.0);
         }
@@ -751,11 +778,20 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
       } else if constexpr (!kLate) {
         L[0][(F + 2) & 3] = load_pair(bkc, p.cur, i + 2);
         Lm[(F + 1) & 1] = load_pair(bkc, p.prev, i + 1);
+        if constexpr (VARC) lq[(F + 1) & 3] = load_pair(bkc, p.lamf, i + 1);  // (S ≤ 3: plane i−3's slot is dead)
       } else {
         // u^n plane i+2 right after the commit: its slot (plane i−2's) has been dead since stage 2 of iteration i−1,
         // and issued here it has the whole iteration (≈ 2 µs) to arrive — after stage 2, as first built, the next
         // commit waited for it: −13 % per 5-step pass (profiles/r5/stores/abn_cur_early.log)
         L[0][(F + 2) & 3] = load_pair(bkc, p.cur, i + 2);
+        if constexpr (VARC) {  // (plane i−3, i−4 for stages 4, 5 first: the load takes plane i−3's slot)
+          static_for<1, kNLqo>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = kNLqo - decltype(jc)::value;
+            lqo[j] = lqo[j - 1];
+          });
+          lqo[0] = lq[(F + 1) & 3];
+          lq[(F + 1) & 3] = load_pair(bkc, p.lamf, i + 1);
+        }
       }
       // (scheduling fences between the load passes' stages: the compiler would otherwise hoist later stages' LDS
       // reads into earlier ones and run out of the 128 VGPRs; the analytic start has the registers to overlap one
@@ -800,6 +836,7 @@ __global__ __launch_bounds__(kNT) void k_leapfrog_p2(const P2Params p) {
     if constexpr (!INIT) {
       L[0][1] = pq[2];
       Lm[0] = pq[3];
+      if constexpr (VARC) lq[0] = pql;
     }
     // head blocks (general) until the first block inside the bulk range, bulk blocks, then the general tail
     const int blo = max(max(wx0, p.sx0), 1 - p.gx0) + (S - 1);

@@ -178,8 +178,12 @@ struct UnitPlan {
 // speed: a coefficient field is set (SpeedPlan). One rank's fused-single mode then runs single steps and k_leapfrog2 pairs
 // wherever the intermediate step needs no check — the tb = false unit list, whatever `tb` says, because only those
 // kernels read a coefficient per node — or single steps only (receivers, sources or a sponge are set too: the cone
-// kernels and k_sponge_box recompute with the constant operator). No unit gets drop_prev.
-enum class SpeedPlan { kNone = 0, kPairs = 1, kSingles = 2 };
+// kernels and k_sponge_box recompute with the constant operator). kFused: the pair-tiled passes' coefficient form
+// (PassArgs::lamf) — the pass split of a stored start at n = 1 (like set_initial's), no deeper than kP2VarcMaxStages;
+// where speed_fused_ok says no (tb off, temporal ≤ 2, several ranks, a box the pair-tiled pass does not take) it is the
+// kPairs plan. No unit gets drop_prev.
+enum class SpeedPlan { kNone = 0, kPairs = 1, kSingles = 2, kFused = 3 };
+bool speed_fused_ok(const RankSchedule& s);
 std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources = false,
                                  SpeedPlan speed = SpeedPlan::kNone);
 

@@ -169,15 +169,17 @@ class GpuSolver {
   // Variable wave speed u_tt = c²(x)·Δu (cpu.hpp speed_to_local; CpuSolver is the definition, the fields match it bit for
   // bit). c: a global (N+1)³ field, face values ignored, interior values finite and > 0; courant()·max c ≤ 1 unless
   // `force`; nullptr clears it. lamf = lam·c² is a fifth device buffer in the solve layout, refused when it does not fit
-  // into free device memory. The LDS pass kernels are untouched: a solve with a speed field runs the VARC instantiations
-  // of the single-step kernels and of k_leapfrog2_rq — single steps and two-step pairs (the tb = false unit list,
-  // whatever `tb` says); single steps only with receivers, sources or a sponge (the cone kernels and k_sponge_box
-  // recompute with the constant operator; k_record_gather and the one-step source add are coefficient-free). The start is
+  // into free device memory. A solve with a speed field runs the VARC instantiations: on the default schedule (temporal
+  // = 5) the pair-tiled passes' (k_leapfrog_p2, up to kP2VarcMaxStages steps per pass, 40/S bytes per node-step;
+  // SpeedPlan::kFused), with temporal ≤ 2, tb = false or a box the pass does not take those of the single-step kernels
+  // and of k_leapfrog2_rq — single steps and two-step pairs (the tb = false unit list); single steps only with
+  // receivers, sources or a sponge (the cone kernels and k_sponge_box recompute with the constant operator;
+  // k_record_gather and the one-step source add are coefficient-free). The start is
   // stored by k_first_step_field<VARC> from step 1 — from set_initial's φ, ψ, else from the eigenmode array kept in
   // init_[0] (no analytic start, no init2); no drop_prev. Everything is on s0, graph-captured, run_batch pipelined.
   // Dropping or setting it drops the captured graph. Refused (messages start with "speed:"): a world larger than 1 of any
   // kind, fake ranks, the push and copy-engine transports, 8 rows per wave (4 with a sponge), set_state, temporal = 3 or 4
-  // (the default 5 stands for "unset" and runs pairs), and energy() — Solver.energy downloads both levels and runs
+  // (a depth of its own; the default 5 runs the deepest built coefficient pass), and energy() — Solver.energy downloads both levels and runs
   // cpu_energy with the mass weight.
   void set_speed(const double* c_global, bool force = false);
   bool speed() const { return lamf_dev_ != nullptr; }
@@ -232,6 +234,12 @@ class GpuSolver {
   // whether the last solve's passes stored u^{K−1} themselves (false: its last pass left it out, UnitPlan::drop_prev,
   // and the first of energy(0), download(1), field_hash(1) rebuilds it)
   bool stored_prev() const { return units_.empty() || !units_.back().drop_prev; }
+  // steps of every unit of the last run()'s plan, in order (1: a single step; ≥ 2: one fused pass)
+  std::vector<int> unit_steps() const {
+    std::vector<int> v;
+    for (const UnitPlan& u : units_) v.push_back(u.steps);
+    return v;
+  }
   // whether the last solve's first pass computed u⁰, u¹ itself (no init kernel; never with receivers)
   bool analytic_start() const { return analytic_; }
 
@@ -359,9 +367,13 @@ class GpuSolver {
   double* lamf_dev_ = nullptr;        // set_speed: lam·c² in the solve layout (null: constant speed 1)
   SpeedRange speed_range_;
   int temporal_asked_ = 0;            // SolverOptions::temporal as given (sch_.opt.temporal may be lowered)
+  bool speed_fused_ = false;          // this solve's units are pair-tiled passes with the coefficient (SpeedPlan::kFused)
   bool speed_eig_ = false;            // init_[0] holds the eigenmode array set_speed put there (no set_initial yet)
   SpeedPlan speed_plan() const {
-    return !speed() ? SpeedPlan::kNone : (recording_ || n_src_ > 0 || sponge()) ? SpeedPlan::kSingles : SpeedPlan::kPairs;
+    return !speed()                                    ? SpeedPlan::kNone
+           : (recording_ || n_src_ > 0 || sponge()) ? SpeedPlan::kSingles
+           : speed_fused_ok(sch_)                     ? SpeedPlan::kFused
+                                                      : SpeedPlan::kPairs;
   }
   double* sponge_dev_ = nullptr;      // sponge layers: the six tables (N + 3 entries each) in device memory ...
   SpongeView sponge_view_;            // ... and their node-0 pointers

@@ -61,6 +61,8 @@ inline bool leapfrog_p2_supported(const Layout& l, const LBox& box, int stages) 
          box.z0 >= full.z0 && box.z1 <= full.z1 && (box.z0 + l.zg + l.zs) % 2 == 0 &&
          (box.z1 == full.z1 || (box.z1 - box.z0) % 2 == 0);
 }
+// deepest pair-tiled pass built with a coefficient field (PassArgs::lamf; kernels_leapfrog_p2_varc_s*.hip)
+constexpr int kP2VarcMaxStages = 4;
 constexpr int kP2MaxBoxes = 6;  // boxes per pair-tiled launch (deep_split: up to 6 shells)
 
 }  // namespace wave3d

@@ -75,8 +75,9 @@ hipStream_t sptr(std::uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 PassArgs py_pass_args(std::uintptr_t prev, std::uintptr_t cur, std::uintptr_t out1, std::uintptr_t out2,
                       std::uintptr_t s, const std::vector<double>& ct, int check_mask, std::uintptr_t partials,
                       const LeapfrogTbTiling& t, const LBox& real, bool analytic_start, int level_stride,
-                      int grid_blocks) {
+                      int grid_blocks, std::uintptr_t lamf = 0) {
   PassArgs a;
+  a.lamf = dptr<const double>(lamf);  // (a speed field's device array in `layout`; 0: constant speed)
   a.prev = dptr<const double>(prev);
   a.cur = dptr<const double>(cur);
   a.out1 = dptr<double>(out1);
@@ -767,9 +768,9 @@ PYBIND11_MODULE(_C, m) {
            std::uintptr_t out2, const LBox& box, std::uintptr_t s, const std::vector<double>& ct, int check_mask,
            std::uintptr_t partials, const LeapfrogTbTiling& t, std::uintptr_t stream, const LBox& real,
            bool analytic_start, int level_stride, int grid_blocks, const std::vector<std::uintptr_t>& pack_zf,
-           int pack_w) {
+           int pack_w, std::uintptr_t lamf) {
           PassArgs a = py_pass_args(prev, cur, out1, out2, s, ct, check_mask, partials, t, real, analytic_start,
-                                    level_stride, grid_blocks);
+                                    level_stride, grid_blocks, lamf);
           TbPack pk;
           TbPack* dev = nullptr;
           if (!pack_zf.empty()) {
@@ -797,22 +798,24 @@ PYBIND11_MODULE(_C, m) {
         py::arg("box"), py::arg("s"), py::arg("ct"), py::arg("check_mask"), py::arg("partials"), py::arg("tiling"),
         py::arg("stream"), py::arg("real") = tb_default_real(), py::arg("analytic_start") = false,
         py::arg("level_stride") = 0, py::arg("grid_blocks") = 0, py::arg("pack_zf") = std::vector<std::uintptr_t>{},
-        py::arg("pack_w") = 0);
+        py::arg("pack_w") = 0, py::arg("lamf") = 0);
   m.def("gpu_leapfrog_p2_partials", &leapfrog_p2_partials);
   m.def("gpu_leapfrog_p2_boxes",
         [](const Layout& l, const Coeffs& c, std::uintptr_t prev, std::uintptr_t cur, std::uintptr_t out1,
            std::uintptr_t out2, const std::vector<LBox>& boxes, std::uintptr_t s, const std::vector<double>& ct,
            int check_mask, std::uintptr_t partials, const LeapfrogTbTiling& t, std::uintptr_t stream, const LBox& real,
-           bool analytic_start, int level_stride, int grid_blocks) {
+           bool analytic_start, int level_stride, int grid_blocks, std::uintptr_t lamf) {
           PassArgs a = py_pass_args(prev, cur, out1, out2, s, ct, check_mask, partials, t, real, analytic_start,
-                                    level_stride, grid_blocks);
+                                    level_stride, grid_blocks, lamf);
           launch_leapfrog_p2_boxes(l, c, boxes.data(), static_cast<int>(boxes.size()), a, sptr(stream));
         },
         py::arg("layout"), py::arg("coeffs"), py::arg("prev"), py::arg("cur"), py::arg("out1"), py::arg("out2"),
         py::arg("boxes"), py::arg("s"), py::arg("ct"), py::arg("check_mask"), py::arg("partials"), py::arg("tiling"),
         py::arg("stream"), py::arg("real") = tb_default_real(), py::arg("analytic_start") = false,
-        py::arg("level_stride") = 0, py::arg("grid_blocks") = 0,
-        "one pair-tiled launch over up to 6 boxes (the overlapped schedules' shells); their partials share one slot");
+        py::arg("level_stride") = 0, py::arg("grid_blocks") = 0, py::arg("lamf") = 0,
+        "one pair-tiled launch over up to 6 boxes (the overlapped schedules' shells); their partials share one slot. "
+        "lamf: a speed field's device array in `layout` (the VARC passes, 2..p2_varc_max_stages steps; 0: constant speed)");
+  m.attr("p2_varc_max_stages") = kP2VarcMaxStages;
   // the host-side workgroup arithmetic of the passes (pass_grid.hpp)
   m.def("p2_launch_blocks", [](const std::vector<LBox>& boxes, const LeapfrogTbTiling& t) {
     const P2LaunchGrid g = p2_launch_grid(boxes.data(), static_cast<int>(boxes.size()), t);
@@ -821,6 +824,34 @@ PYBIND11_MODULE(_C, m) {
       per.emplace_back(g.box[k].nty, g.box[k].ntz, g.box[k].xlen, g.box[k].nxc, g.box[k].blk0);
     return py::make_tuple(g.nblocks, per);
   });
+  // the unit plan of a one-rank solve (schedule.cpp, host only): speed = 0 none, 1 pairs, 2 singles, 3 fused (SpeedPlan)
+  m.def("plan_units", [](const Problem& p, const SolverOptions& o, int start_n, bool analytic, bool sources, int speed) {
+    W3D_REQUIRE(speed >= 0 && speed <= 3, "plan_units: speed plan 0..3");
+    const RankSchedule s = make_rank_schedule(p, o, 0, 1, 1e13);
+    // lds_pass: the unit is one LDS S-step pass, which checks any of its levels (PassArgs::check_mask); every other
+    // unit (a single step, a k_leapfrog2 pair) checks its last level only. checked: the unit's levels n + k that are
+    // check steps of the schedule (RankSchedule::is_check, what GpuSolver builds the pass's check mask from)
+    const SpeedPlan sp = static_cast<SpeedPlan>(speed);
+    const bool passes = sp == SpeedPlan::kNone ? (s.mode == Mode::kFusedSingle && s.opt.tb) || s.mode == Mode::kDeepTb
+                                               : sp == SpeedPlan::kFused && speed_fused_ok(s);
+    py::list out;
+    for (const UnitPlan& u : plan_units(s, start_n, analytic, sources, sp)) {
+      py::dict d;
+      d["lds_pass"] = passes && u.fused();
+      py::list chk;
+      for (int k = 1; k <= u.steps; ++k)
+        if (s.is_check(u.n + k)) chk.append(u.n + k);
+      d["checked"] = chk;
+      d["n"] = u.n;
+      d["steps"] = u.steps;
+      d["analytic"] = u.analytic;
+      d["drop_prev"] = u.drop_prev;
+      d["exchange"] = u.exchange;
+      out.append(d);
+    }
+    return out;
+  }, py::arg("problem"), py::arg("options"), py::arg("start_n") = 1, py::arg("analytic") = false,
+     py::arg("sources") = false, py::arg("speed") = 0);
   m.def("tb_slot_blocks", &tb_slot_blocks);
   m.def("tb_shells_launch_blocks", [](const Layout& l, const std::vector<LBox>& boxes, const LeapfrogTbTiling& t,
                                       int slot) {
@@ -1031,6 +1062,7 @@ PYBIND11_MODULE(_C, m) {
       .def("device_bytes", &GpuSolver::device_bytes)
       .def_property_readonly("mode", &GpuSolver::mode)
       .def_property_readonly("stored_prev", &GpuSolver::stored_prev)
+      .def_property_readonly("unit_steps", &GpuSolver::unit_steps)
       .def_property_readonly("graph_enabled", [](const GpuSolver& s) { return s.options().graph; });
 
   // the CLI's multi-rank schedule autotune (runtime_autotune.cpp): same candidates, same rules; collectives over the

@@ -192,6 +192,9 @@ void leapfrog_p2_prepare() {
   prepare_p2_box_s3();
   prepare_p2_box_s4();
   prepare_p2_box_s5();
+  prepare_p2_varc_s2();
+  prepare_p2_varc_s3();
+  prepare_p2_varc_s4();
 }
 
 void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const LBox* boxes, int nbox, const PassArgs& a,
@@ -201,6 +204,17 @@ void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const LBox* boxe
   // pass, or z-face packing, never reaches this launcher without one of them: pass_kernel)
   W3D_REQUIRE(a.out1 != nullptr || (t.ghost_x1 == 0 && a.pack == nullptr && a.push == nullptr),
               "leapfrog_p2: a pass without u^{n+S-1} (out1 = null) cannot store its ghost planes (ghost_x1) or pack");
+  if (a.lamf != nullptr) {  // a speed field: the VARC load passes, or a refusal — never the constant operator
+    W3D_REQUIRE(!a.analytic_start, "speed: the analytic-start pass has no coefficient form (a speed solve has a stored start)");
+    W3D_REQUIRE(a.out1 != nullptr, "speed: a pass without u^{n+S-1} (out1 = null) is not built with a coefficient field");
+    W3D_REQUIRE(a.pack == nullptr && a.push == nullptr, "speed: no push transport or fused pack with a coefficient field");
+    W3D_REQUIRE(t.stages >= 2 && t.stages <= kP2VarcMaxStages,
+                "speed: the pair-tiled pass with a coefficient field is built for 2.." + std::to_string(kP2VarcMaxStages) +
+                    " steps, not " + std::to_string(t.stages));
+    for (int k = 0; k < nbox; ++k)
+      W3D_REQUIRE(leapfrog_p2_supported(l, boxes[k], t.stages),
+                  "speed: the pair-tiled pass does not take this box (whole pairs inside the rank's y/z range)");
+  }
   P2Params p = make_plan_p2(l, boxes, nbox, t, a.real, a.analytic_start);
   if (!fill_pass_params(p, l, c, a, "leapfrog_p2")) return;
   if (a.analytic_start) {  // (the analytic start reads neither: any valid buffer)
@@ -210,7 +224,13 @@ void launch_leapfrog_p2_boxes(const Layout& l, const Coeffs& c, const LBox* boxe
 #ifdef W3D_EXPERIMENT_WGTIME
   p.wgtime = wgtime_slot(p.nblocks, t.stages, a.analytic_start);
 #endif
-  if (c.box) {  // (a rectangular box: the BOX instantiations; a cube launches exactly what it always did)
+  if (a.lamf != nullptr) {
+    switch (t.stages) {
+      case 2: launch_p2_varc_s2(p, p.nblocks, c.box, stream); break;
+      case 3: launch_p2_varc_s3(p, p.nblocks, c.box, stream); break;
+      default: launch_p2_varc_s4(p, p.nblocks, c.box, stream); break;
+    }
+  } else if (c.box) {  // (a rectangular box: the BOX instantiations; a cube launches exactly what it always did)
     switch (t.stages) {
       case 2: launch_p2_box_s2(p, p.nblocks, a.analytic_start, stream); break;
       case 3: launch_p2_box_s3(p, p.nblocks, a.analytic_start, stream); break;

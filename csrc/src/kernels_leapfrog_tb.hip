@@ -88,6 +88,8 @@ void launch_leapfrog_tb(const Layout& l, const Coeffs& c, const LBox& box, const
     launch_leapfrog_p2_boxes(l, c, &box, 1, a, stream);
     return;
   }
+  W3D_REQUIRE(a.lamf == nullptr, "speed: k_leapfrog_tb (tiling.p2 off, the push transport, the fused pack, or a box the "
+                                 "pair-tiled pass does not take) has no form with a coefficient field");
   W3D_REQUIRE(t.stages <= 4, "leapfrog_tb: 5-step passes need the pair-tiled kernel (tiling.p2)");
   W3D_REQUIRE(t.ghost_x1 == 0, "leapfrog_tb: ghost-plane stores (tiling.ghost_x1) need the pair-tiled kernel");
   W3D_REQUIRE(a.out1 != nullptr, "leapfrog_tb: a pass without u^{n+S-1} (out1 = null) needs the pair-tiled kernel");

@@ -185,17 +185,21 @@ bool runs_p2(const RankSchedule& s, int stages, bool analytic) {
 // steps with every 2nd level checked, measured at 512³ (tools/tune_leapfrog.py --tb); the analytic first pass reads
 // nothing but computes u⁰, u¹ (compute-bound). Slab and block ranks (deep-tb) take passes of ≥ 2 steps only: every
 // pass writes the two levels the next one reads, so each exchange is one message pair per face.
-void plan_passes(const RankSchedule& s, int n, bool analytic, std::vector<UnitPlan>& units) {
+void plan_passes(const RankSchedule& s, int n, bool analytic, std::vector<UnitPlan>& units, bool varc = false) {
   static const double kStepCostTb[6] = {0.0, 610.0, 437.0, 302.0, 258.0, 1e9};
   // (analytic: φ-stage start, re-measured)
   static const double kAnalyticCostTb[6] = {0.0, 1e9, 346.0, 300.0, 318.0, 1e9};
   // the pair-tiled passes (k_leapfrog_p2, one rank): µs per step at 512³ (profiles/r5/)
   static const double kStepCostP2[6] = {0.0, 610.0, 430.0, 290.0, 225.0, 180.0};
   static const double kAnalyticCostP2[6] = {0.0, 1e9, 300.0, 200.0, 135.0, 1e9};
+  // ... with a coefficient field (VARC, 512³, profiles/speed_fused/README.md): the single step 853, the 3-step pass
+  // 995–1007 and the 4-step pass 1170 µs per launch; the 2-step pass was not timed at 512³ and stands at the constant
+  // pass's 430 times the byte ratio 1.25. No 5-step pass is built.
+  static const double kStepCostVarc[6] = {0.0, 853.0, 538.0, 333.0, 292.0, 1e9};
   const bool p2 = runs_p2(s, 2, false);
-  const double* kStepCost = p2 ? kStepCostP2 : kStepCostTb;
+  const double* kStepCost = varc ? kStepCostVarc : p2 ? kStepCostP2 : kStepCostTb;
   const double* kAnalyticCost = p2 ? kAnalyticCostP2 : kAnalyticCostTb;
-  const int K = s.prob.K, rem = K - n, smax = s.opt.temporal, smin = s.mode == Mode::kDeepTb ? 2 : 1;
+  const int K = s.prob.K, rem = K - n, smax = std::min(s.opt.temporal, varc ? kP2VarcMaxStages : 5), smin = s.mode == Mode::kDeepTb ? 2 : 1;
   std::vector<double> best(static_cast<size_t>(rem + 1), 1e300);
   std::vector<int> take(static_cast<size_t>(rem + 1), 1);
   best[0] = 0.0;
@@ -260,13 +264,22 @@ void plan_msgs(const RankSchedule& s, UnitPlan& u) {
 
 }  // namespace
 
+bool speed_fused_ok(const RankSchedule& s) {
+  return s.world == 1 && s.mode == Mode::kFusedSingle && s.opt.tb && s.opt.temporal >= 3 && !s.push && !s.sdma &&
+         runs_p2(s, 2, false);
+}
+
 std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources, SpeedPlan speed) {
   std::vector<UnitPlan> units;
   const int K = s.prob.K;
   int n = start_n;
   const bool varc = speed != SpeedPlan::kNone;
   W3D_REQUIRE(!varc || (s.world == 1 && !analytic), "speed: one rank and a stored start only");
-  if (((s.mode == Mode::kFusedSingle && s.opt.tb) || s.mode == Mode::kDeepTb) && !varc) {
+  if (speed == SpeedPlan::kFused && !speed_fused_ok(s)) speed = SpeedPlan::kPairs;  // (e.g. a box the pass does not take)
+  if (speed == SpeedPlan::kFused) {
+    // the split of a stored start by the coefficient passes' own measured costs, no deeper than they are built
+    plan_passes(s, n, false, units, true);
+  } else if (((s.mode == Mode::kFusedSingle && s.opt.tb) || s.mode == Mode::kDeepTb) && !varc) {
     plan_passes(s, n, analytic, units);
   } else if (s.mode == Mode::kFusedSingle) {
     while (n <= K - 1) {

@@ -203,8 +203,9 @@ void GpuSolver::set_speed(const double* c, bool force) {
               "speed: with a sponge the register-queue single step is built for 1 or 2 rows per wave only");
   W3D_REQUIRE(resume_n_ == 0, "speed: not together with set_state / --resume");
   W3D_REQUIRE(temporal_asked_ <= 2 || temporal_asked_ == SolverOptions{}.temporal,
-              "speed: temporal = " + std::to_string(temporal_asked_) + " asks for fused passes of more than two steps, which "
-              "have no coefficient form; use temporal = 1 or 2 (the default runs two-step pairs)");
+              "speed: temporal = " + std::to_string(temporal_asked_) + " asks for a pass depth of its own, which a solve with "
+              "a coefficient field does not take; leave temporal at its default (fused passes of up to " +
+              std::to_string(kP2VarcMaxStages) + " steps) or use temporal = 1 or 2 (single steps and two-step pairs)");
   std::vector<double> host(static_cast<size_t>(sch_.lay.total));
   const SpeedRange r = speed_to_local(sch_.prob, sch_.lay, c, host.data(), nullptr);
   speed_cfl(sch_.prob, r, force);
@@ -595,6 +596,7 @@ void GpuSolver::phase_init() {
   old_ = 0;
   // (sponge layers: like sources, the last pass keeps both levels — a rebuild would need the slabs' recomputation too)
   units_ = plan_units(sch_, start_n_, analytic_, n_src_ > 0 || sponge(), speed_plan());
+  speed_fused_ = speed_plan() == SpeedPlan::kFused;  // (the units are pair-tiled passes that read lamf)
   if (sch_.push) push_upload();
 }
 
@@ -743,6 +745,7 @@ PassArgs GpuSolver::tb_args_fields(const UnitPlan& u, int prev, int cur, int out
   a.grid_blocks = n_tb_;
   a.real = sch_.mode == Mode::kDeepTb ? sch_.sreal : tb_default_real();
   a.analytic_start = u.analytic;
+  a.lamf = speed_fused_ ? lamf_dev_ : nullptr;  // (a speed field: the passes' coefficient form)
   return a;
 }
 
@@ -826,7 +829,8 @@ void GpuSolver::unit_interior(int i) {
       });
     }
     np = off + n_dint_;
-  } else if ((sch_.mode == Mode::kFusedSingle && sch_.opt.tb && u.fused() && !speed()) || sch_.mode == Mode::kDeepTb) {
+  } else if ((sch_.mode == Mode::kFusedSingle && sch_.opt.tb && u.fused() && (!speed() || speed_fused_)) ||
+             sch_.mode == Mode::kDeepTb) {
     // S steps in one LDS pass (on slab ranks: the interior left between this unit's shells); every checked level
     // has its own block of partials
     if (sch_.mode != Mode::kDeepTb) tb_slots_ = 0;

@@ -149,8 +149,9 @@ class Solver:
                 raise ValueError("speed: one GPU rank that spans the domain only (no group, push or copy-engine "
                                  "transport)")
             if temporal in (3, 4):
-                raise ValueError(f"speed: temporal={temporal} asks for fused passes of more than two steps, which have "
-                                 "no coefficient form; use temporal=1 or 2 (the default runs two-step pairs)")
+                raise ValueError(f"speed: temporal={temporal} asks for a pass depth of its own, which a solve with a "
+                                 "coefficient field does not take; leave temporal at its default (fused passes of up to "
+                                 "four steps) or use temporal=1 or 2 (single steps and two-step pairs)")
         self._impl = None
         self._initial = None  # (set_initial's global phi, psi: a group's E(1/2) is computed from them on the host)
         if runtime not in ("inproc", "process"):
@@ -398,7 +399,9 @@ class Solver:
         """Variable wave speed: every following run() solves u_tt = c(x)²·Δu with ``c`` a GLOBAL (N+1)³ float64 array
         or tensor (face values ignored; interior values finite and > 0; courant·max c ≤ 1 unless ``force``, default
         the constructor's). ``None`` clears it. ``CpuSolver`` is the definition; one HIP rank that spans the domain
-        matches it bit for bit on single steps and two-step pairs (``temporal`` 1, 2 or the default). The error
+        matches it bit for bit: fused passes of up to four steps with the coefficient on the default schedule
+        (``temporal`` 3 and 4 are refused), two-step pairs and single steps with ``temporal`` 1 or 2 or ``tb=False``, single steps only
+        with receivers, sources or a sponge. The error
         columns then mean nothing; ``energy`` carries the mass weight 1/c². Not with ``set_state``."""
         import numpy as np
 

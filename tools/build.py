@@ -66,6 +66,10 @@ LIB_SOURCES = [
     ("src/kernels_leapfrog_p2_box_s3.hip", "hip"),
     ("src/kernels_leapfrog_p2_box_s4.hip", "hip"),
     ("src/kernels_leapfrog_p2_box_s5.hip", "hip"),
+    # speed-field instantiations of the pair-tiled pass (cube and box per stage count)
+    ("src/kernels_leapfrog_p2_varc_s2.hip", "hip"),
+    ("src/kernels_leapfrog_p2_varc_s3.hip", "hip"),
+    ("src/kernels_leapfrog_p2_varc_s4.hip", "hip"),
     ("src/comm.cpp", "hip"),
     ("src/solver_gpu.cpp", "hip"),
     ("src/gpu_group.cpp", "hip"),

@@ -124,6 +124,9 @@ constexpr Personality kPersonalities[] = {
                "                     --force). One GPU rank (fused passes of up to 4 steps; --temporal 1 or 2 / --no-tb: single\n"
                "                     steps and two-step pairs; --temporal 3 or 4 refused; with receivers, sources or a sponge: single steps) or --cpu;\n"
                "                     not with --resume. The error lines then have no meaning\n"
+               "  --order 2|4        spatial order of the Laplacian (default 2). 4: the 13-point stencil with the odd reflection\n"
+               "                     u(-1) = -u(1) at the walls; stable for courant <= sqrt(3)/2; one GPU rank (single steps) or\n"
+               "                     --cpu; not with --sponge, --speed, --resume, --energy, --np, --group, --serve, --fake-rank\n"
                "  --force            run even if the CFL condition is violated\n"
                "  --quiet            only the summary\n");
   std::exit(2);
@@ -277,6 +280,11 @@ Args parse(int argc, char** argv) {
       a.prob.sponge = sp;
     }
     else if (s == "--force") a.force = true;
+    else if (s == "--order") {
+      const std::string v = next();
+      if (v != "2" && v != "4") usage("order: --order expects 2 or 4");
+      a.prob.order = v == "4" ? 4 : 2;
+    }
     else if (s == "--quiet") a.quiet = true;
     else if (s == "-h" || s == "--help") usage();
     else if (!s.empty() && s[0] == '-' && s.size() > 1 && !std::isdigit(static_cast<unsigned char>(s[1])) && s[1] != '.')
@@ -316,6 +324,14 @@ Args parse(int argc, char** argv) {
   if (!a.speed.empty() && (a.np > 1 || a.group > 0 || a.serve || a.fake_rank >= 0))
     usage("speed: one rank only (not with --np, --group, --serve or --fake-rank)");
   if (!a.speed.empty() && !a.resume.empty()) usage("speed: not together with --resume");
+  if (a.prob.order == 4) {
+    if (a.np > 1 || a.group > 0 || a.serve || a.fake_rank >= 0)
+      usage("order: --order 4 runs on one rank only (not with --np, --group, --serve or --fake-rank)");
+    if (!a.resume.empty()) usage("order: --order 4 not together with --resume");
+    if (!a.speed.empty()) usage("order: --order 4 takes no --speed field");
+    if (a.prob.sponge.on()) usage("order: --order 4 takes no --sponge");
+    if (a.energy) usage("order: --energy is the second-order discrete energy, which --order 4 does not conserve");
+  }
   if (a.repeat < 1) a.repeat = 1;
   return a;
 }
@@ -351,6 +367,7 @@ std::string box_json(const Problem& p) {
   if (!p.is_box()) return "";
   return ", \"box\": [" + jexact(p.L) + ", " + jexact(p.edge_y()) + ", " + jexact(p.edge_z()) + "]";
 }
+std::string order_json(const Problem& p) { return p.order == 2 ? "" : ", \"order\": " + std::to_string(p.order); }
 std::string sponge_json(const Problem& p) {
   if (!p.sponge.on()) return "";
   return ", \"sponge\": [" + std::to_string(p.sponge.width) + ", " + jexact(p.sponge.sigma) + ", " +

@@ -88,7 +88,7 @@ int run_cpu(const Args& a) {
   if (!a.json.empty()) {
     std::ofstream j(a.json);
     j << "{\"backend\": \"cpu\", \"N\": " << a.prob.N << ", \"tau\": " << jnum(a.prob.tau) << ", \"K\": "
-      << a.prob.K << ", \"L\": " << jnum(a.prob.L) << box_json(a.prob) << sponge_json(a.prob) << ", \"ranks\": 1, \"dims\": [1, 1, 1], \"threads\": "
+      << a.prob.K << ", \"L\": " << jnum(a.prob.L) << box_json(a.prob) << sponge_json(a.prob) << order_json(a.prob) << ", \"ranks\": 1, \"dims\": [1, 1, 1], \"threads\": "
       << cpu_max_threads() << ", \"solve_s\": " << jnum(best) << ", \"mean_s\": " << jnum(sum / a.repeat)
       << ", \"gcell_per_s\": " << jnum(gcell) << ", \"schedule\": \"cpu-openmp\", \"bench_steps\": " << a.bench_steps
       << ", \"bench_s\": " << jnum(bench_s) << ", \"finite\": " << (r.finite ? "true" : "false")
@@ -150,7 +150,7 @@ int run_cpu_rank(const Args& a, ShmGroup& g, int rank) {
         std::ofstream j(a.json);
         j << "{\"backend\": \"cpu\", \"ranks\": " << g.world() << ", \"dims\": [" << d.px << ", " << d.py << ", "
           << d.pz << "], \"N\": " << a.prob.N << ", \"tau\": " << a.prob.tau << ", \"K\": " << a.prob.K
-          << ", \"L\": " << a.prob.L << box_json(a.prob) << sponge_json(a.prob) << ", \"threads\": " << cpu_max_threads() << ", \"solve_s\": " << best
+          << ", \"L\": " << a.prob.L << box_json(a.prob) << sponge_json(a.prob) << order_json(a.prob) << ", \"threads\": " << cpu_max_threads() << ", \"solve_s\": " << best
           << ", \"mean_s\": " << sum / a.repeat << ", \"exchange_s\": " << exch << ", \"gcell_per_s\": " << gcell
           << ", \"final_max_err\": " << (r.max_err.empty() ? 0.0 : r.max_err.back())
           << ", \"final_rms_err\": " << (r.rms_err.empty() ? 0.0 : r.rms_err.back())

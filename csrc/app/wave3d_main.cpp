@@ -203,7 +203,7 @@ int run_group(const Args& a, const SolverOptions& o, const hipDeviceProp_t& prop
   if (!a.json.empty()) {
     std::vector<int> cc = g.comm_counts();
     std::ofstream j(a.json);
-    j << "{\"backend\": \"hip\", \"group\": " << a.group << box_json(a.prob) << sponge_json(a.prob) << ", \"transport\": " << jstr(a.group_transport)
+    j << "{\"backend\": \"hip\", \"group\": " << a.group << box_json(a.prob) << sponge_json(a.prob) << order_json(a.prob) << ", \"transport\": " << jstr(a.group_transport)
       << ", \"graph\": " << (g.graph_enabled() ? "true" : "false") << ", \"schedule\": " << jstr(g.rank(0).mode())
       << ", \"temporal\": " << g.rank(0).options().temporal << ", \"stored_prev\": "
       << (g.rank(0).stored_prev() ? "true" : "false") << ", \"rccl_comms\": " << cc.size() << ", \"solve_s\": " << jnum(best);
@@ -451,7 +451,7 @@ int run_gpu(const Args& a) {
     if (!a.json.empty()) {
       std::ofstream j(a.json);
       j << "{\"backend\": \"hip\", \"N\": " << a.prob.N << ", \"tau\": " << jnum(a.prob.tau) << ", \"K\": " << a.prob.K
-        << ", \"L\": " << jnum(a.prob.L) << box_json(a.prob) << sponge_json(a.prob) << ", \"ranks\": " << world << ", \"dims\": [" << d.px << ", " << d.py
+        << ", \"L\": " << jnum(a.prob.L) << box_json(a.prob) << sponge_json(a.prob) << order_json(a.prob) << ", \"ranks\": " << world << ", \"dims\": [" << d.px << ", " << d.py
         << ", " << d.pz << "], \"solve_s\": " << jnum(best) << ", \"mean_s\": " << jnum(mean)
         << ", \"first_s\": " << jnum(first) << ", \"process_s\": " << jnum(t_proc) << ", \"rccl_init_s\": "
         << jnum(t_comm) << ", \"rccl_nranks\": " << rccl_nranks << ", \"rccl_version\": " << rccl_version()
@@ -516,7 +516,14 @@ int main(int argc, char** argv) {
   try {
     Args a = parse(argc, argv);
     a.prob.validate();
-    if (!a.prob.cfl_ok()) {
+    if (a.prob.order == 4 && !a.prob.cfl_ok_eff()) {
+      std::fprintf(stderr,
+                   "wave3d: CFL violated: courant = %.4f > sqrt(3)/2 for --order 4 (effective %.4f > 1, tau_max = %.3e for "
+                   "N=%lld); the leapfrog scheme is unstable.%s\n",
+                   a.prob.courant(), a.prob.courant_eff(), a.prob.tau_max() * (std::sqrt(3.0) / 2.0),
+                   static_cast<long long>(a.prob.N), a.force ? " Continuing (--force)." : " Use a smaller tau, or --force.");
+      if (!a.force) return 2;
+    } else if (a.prob.order != 4 && !a.prob.cfl_ok()) {
       if (a.prob.is_box())
         std::fprintf(stderr,
                      "wave3d: CFL violated: courant = tau*sqrt(1/hx^2+1/hy^2+1/hz^2) = %.4f > 1 (tau_max = %.3e for "

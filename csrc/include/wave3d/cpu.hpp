@@ -147,6 +147,7 @@ void cpu_init_first(const Layout& l, const Coeffs& c, const double* s, double* u
 // and outside the global boundary and in the padding. phi / psi: local arrays in `src` = initial_layout(...), filled
 // by initial_to_local. With ψ absent and φ the eigenmode array, u1 equals cpu_init_first's bit for bit.
 // lamf != nullptr (a speed field, layout `l`): the node's coefficient is 0.5·lamf[p] (exact) instead of Coeffs::half_lam.
+// Coeffs::order = 4: Δ_h is the fourth-order operator (stencil.hpp d4sum_t) with the odd reflection at nodes 1 and N − 1.
 void cpu_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
                           const double* psi, double* u0, double* u1, const double* lamf = nullptr);
 
@@ -176,6 +177,8 @@ inline double energy_value(const Problem& p, double kin, double pot) {
 // sponge != nullptr: the damped update (stencil.hpp leapfrog_damped) with the node's g = max, r = min of the three 1-D
 // tables (problem.hpp sponge_tables; global indices); a node with g = 0 gets the undamped bits.
 // lamf != nullptr: a speed field (speed_to_local, layout `l`) — the coefficient of node p is lamf[p] instead of Coeffs::lam.
+// Coeffs::order = 4: the fourth-order operator (stencil.hpp d4sum_t; a layout that spans the domain, no sponge, no lamf).
+// A neighbour at distance 2 of node 1 / N − 1 of an axis is the odd reflection −u, never a load: the ghost layer is not read.
 void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox& box,
                   const double* s, double ct, ErrAcc* acc, const SpongeView* sponge = nullptr,
                   const double* lamf = nullptr);
@@ -283,6 +286,9 @@ class CpuSolver {
  public:
   CpuSolver(const Problem& p, int check_every = 2, int threads = 0);
   CpuResult run();
+  // Problem::order = 4: every step uses the fourth-order operator, the start (eigenmode or set_initial) goes through
+  // cpu_first_step_field; a box, receivers and sources work as before. Refused with messages starting "order:": a sponge
+  // (Problem::validate), set_speed, energy / energy_sums, set_state.
   // With Problem::sponge set every step is the damped one (stencil.hpp leapfrog_damped); the start levels, set_initial,
   // set_state, receivers, sources (added after the damped step, as after the plain one) and energy work as before. The
   // error columns then have no meaning, and the energy decays.

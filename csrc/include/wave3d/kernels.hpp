@@ -44,6 +44,7 @@ void launch_init_two(const Layout& l, const Coeffs& c, const double* d_s, double
 // buffers in `src` = make_layout(prob, box, 16, l.xg + 1, l.yg + 1, l.zg + 1) filled by initial_to_local (cpu.hpp).
 // lamf != nullptr (a speed field, cpu.hpp speed_to_local: device array in layout `l`): the VARC instantiation, the node's
 // coefficient is 0.5·lamf[p] — bit-identical to cpu_first_step_field with the same array.
+// Coeffs::order = 4: the ORDER4 instantiation (d4sum_t, −centre for a distance-2 neighbour outside the grid; no lamf).
 void launch_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
                              const double* psi, double* u0, double* u1, hipStream_t stream, const double* lamf = nullptr);
 
@@ -98,6 +99,19 @@ bool leapfrog_speed_supported(const LeapfrogTiling& t, bool sponge);
 void launch_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox* boxes, int nbox,
                      const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream,
                      const SpongeView* sponge = nullptr, const double* lamf = nullptr);
+
+// The fourth-order single step (kernels_stencil4.hip, k_leapfrog4; Problem::order = 4, Coeffs::order = 4 whose lam carries
+// the 1/12): launch_leapfrog's contract — up to 6 boxes inside the global interior in one launch, in place over u^{n−1},
+// partials per workgroup in launch order (leapfrog4_blocks of them) — on one rank's layout that spans the whole domain.
+// Bit-identical to cpu_leapfrog with the same coefficients. Its tile is leapfrog4_ty(t) = 8 or 16 rows (t.ty below 16:
+// 8; four rows have fewer threads than halo slots); t.variant / t.rows are not looked at. min_chunk: the fewest planes
+// of an x chunk (each chunk re-reads four planes). The ghost layer, the row padding and the planes outside the grid are
+// never used as data: the distance-2 neighbour of node 1 / N − 1 is −centre.
+int leapfrog4_ty(const LeapfrogTiling& t);
+int leapfrog4_blocks(const Layout& l, const LBox* boxes, int nbox, const LeapfrogTiling& t, int min_chunk = 16);
+void launch_leapfrog4(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox* boxes, int nbox,
+                      const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream,
+                      int min_chunk = 16);
 
 // Sponge layers on the fused schedule (kernels_sponge.hip). An LDS pass of `steps` steps runs undamped; its two stored
 // outputs differ from the damped levels only on the slabs cpu.hpp sponge_boxes returns, which this recomputes from the

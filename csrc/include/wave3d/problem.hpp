@@ -37,6 +37,7 @@ struct Problem {
   double Ly = 0.0;    // edge lengths in y and z of a rectangular box; ≤ 0: "= L"
   double Lz = 0.0;
   Sponge sponge;      // absorbing layers (off by default)
+  int order = 2;      // spatial order of the Laplacian: 2 (7-point) or 4 (13-point, stencil.hpp d4sum_t)
 
   double Lx() const { return L; }
   double edge_y() const { return Ly > 0.0 ? Ly : L; }
@@ -63,7 +64,12 @@ struct Problem {
   // Courant number for the 3D 7-point leapfrog: stable iff τ·sqrt(Σ 1/h_d²) ≤ 1 (cube: τ·sqrt(3)/h).
   double courant() const { return is_box() ? tau * std::sqrt(inv_h2_sum()) : tau * std::sqrt(3.0) / h(); }
   bool cfl_ok() const { return courant() <= 1.0; }
-  // Largest stable τ for this grid.
+  // Order-aware guard. The largest symbol of −h²D₄ is 16/3 against 4 for the second-order difference, so the fourth-
+  // order leapfrog is stable iff τ·sqrt(Σ 1/h_d²) ≤ sqrt(3)/2: the effective Courant number is courant()·2/sqrt(3).
+  // order = 2: courant() itself, the same bits.
+  double courant_eff() const { return order == 4 ? courant() * (2.0 / std::sqrt(3.0)) : courant(); }
+  bool cfl_ok_eff() const { return courant_eff() <= 1.0; }
+  // Largest stable τ for this grid (second-order operator; order 4: sqrt(3)/2 of it).
   double tau_max() const { return is_box() ? 1.0 / std::sqrt(inv_h2_sum()) : h() / std::sqrt(3.0); }
   // Cell updates of one full solve (reference convention for GCell/s: N³·K).
   double cell_updates() const { return static_cast<double>(N) * N * N * K; }
@@ -74,6 +80,9 @@ struct Problem {
     W3D_REQUIRE(K >= 1, "K must be >= 1");
     W3D_REQUIRE(L > 0.0 && std::isfinite(L), "L must be > 0");
     W3D_REQUIRE(std::isfinite(Ly) && std::isfinite(Lz), "box edges must be finite");
+    W3D_REQUIRE(order == 2 || order == 4, "order: the spatial order must be 2 or 4");
+    W3D_REQUIRE(order == 2 || !sponge.on(), "order: no sponge layers with order = 4 (the damped form of the fourth-order "
+                                            "operator is a follow-up)");
     W3D_REQUIRE(sponge.width >= 0, "sponge: the width must be >= 0");
     W3D_REQUIRE(!sponge.on() || 2 * static_cast<i64>(sponge.width) <= N - 1,
                 "sponge: two layers of width " + std::to_string(sponge.width) + " do not fit into the " +
@@ -89,12 +98,13 @@ struct Coeffs {
   double ihx2, ihy2, ihz2;  // 1/h_d²
   double tau2;              // τ²
   double half_tau2;         // τ²/2
-  double lam;               // τ²/h²: the update coefficient of d2sum (stencil.hpp)
-  double half_lam;          // (τ²/2)/h²
+  double lam;               // τ²/h²: the update coefficient of d2sum (stencil.hpp); order 4: τ²/(12h²), that of d4sum_t
+  double half_lam;          // (τ²/2)/h²; order 4: (τ²/2)/(12h²)
   // Rectangular box (stencil.hpp::d2sum_box): the y and z differences are weighted by h_x²/h_y², h_x²/h_z² and lam,
   // half_lam carry 1/h_x². `box` selects that form in every kernel; a cube has box = false, ry = rz = 1.
   double ry = 1.0, rz = 1.0;
   bool box = false;
+  int order = 2;            // Problem::order
 
   // force_box (tests): the box form also for a cube — with ry = rz = 1 it must reproduce the cube form's bits
   static Coeffs from(const Problem& p, bool force_box = false) {
@@ -115,6 +125,11 @@ struct Coeffs {
       c.rz = (h * h) / (hz * hz);
     }
     c.box = p.is_box() || force_box;
+    c.order = p.order;
+    if (p.order == 4) {  // (the 1/12 of the fourth-order difference; order 2 never comes here: no bit of it changes)
+      c.lam = c.lam / 12.0;
+      c.half_lam = c.half_lam / 12.0;
+    }
     return c;
   }
 };

@@ -182,6 +182,7 @@ struct UnitPlan {
 // (PassArgs::lamf) — the pass split of a stored start at n = 1 (like set_initial's), no deeper than kP2VarcMaxStages;
 // where speed_fused_ok says no (tb off, temporal ≤ 2, several ranks, a box the pair-tiled pass does not take) it is the
 // kPairs plan. No unit gets drop_prev.
+// Problem::order = 4: single steps only (one rank), whatever the mode, temporal and tb; no unit is analytic or gets drop_prev.
 enum class SpeedPlan { kNone = 0, kPairs = 1, kSingles = 2, kFused = 3 };
 bool speed_fused_ok(const RankSchedule& s);
 std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analytic, bool sources = false,

@@ -166,6 +166,13 @@ class GpuSolver {
   // transports, tb = false (k_leapfrog2 pairs), and a receiver or source within W + temporal nodes of a damped face (the
   // cone kernels recompute with the undamped operator, which equals the damped one only outside that reach).
   bool sponge() const { return sch_.prob.sponge.on(); }
+  // Problem::order = 4: the fourth-order operator (stencil.hpp d4sum_t; CpuSolver is the definition, the fields, the
+  // error log and the traces match it bit for bit). Every unit is a single k_leapfrog4 step whatever temporal and tb say;
+  // the start — the eigenmode array or set_initial's φ, ψ — is the first-step-field kernel's fourth-order form; receivers
+  // use the single-step gather, sources the single-step add; the solve stays graph-captured. Refused (messages start with
+  // "order:"): a world larger than 1 of any kind and group ranks (the halo would be two deep per step), fake ranks, the
+  // push and copy-engine transports, a sponge (Problem::validate), set_speed, energy / energy_sums, set_state.
+  bool order4() const { return sch_.prob.order == 4; }
   // Variable wave speed u_tt = c²(x)·Δu (cpu.hpp speed_to_local; CpuSolver is the definition, the fields match it bit for
   // bit). c: a global (N+1)³ field, face values ignored, interior values finite and > 0; courant()·max c ≤ 1 unless
   // `force`; nullptr clears it. lamf = lam·c² is a fifth device buffer in the solve layout, refused when it does not fit
@@ -324,6 +331,7 @@ class GpuSolver {
   bool own_s0_ = true;  // false: a GpuGroup "push" rank on the group's shared compute stream
   hipEvent_t ev_shell_ = nullptr, ev_halo_ = nullptr, ev_packed_ = nullptr;
   int n_full_ = 0, n_shell_ = 0, n_int_ = 0, n_fused_ = 0;  // error partials of each launch kind
+  int n_full4_ = 0;                                         // ... of the fourth-order single step (order4())
   int n_tb_ = 0;                                            // ... per level of a k_leapfrog_tb pass
   // deep-tb: per level, the partials of this unit's launches (shell lo, shell hi, interior) follow each other
   int tb_slots_ = 0;                                        // launches of the current unit with partials so far

@@ -54,6 +54,35 @@ W3D_HD double d2sum_t(double c, double xm, double xp, double ym, double yp, doub
     return d2sum(c, xm, xp, ym, yp, zm, zp);
 }
 
+// Fourth-order operator (Problem::order = 4). Per axis 12h²·D₄u_i = −u_{i−2} + 16u_{i−1} − 30u_i + 16u_{i+1} − u_{i+2},
+// evaluated as fma(16, m1 + p1, fma(−30, c, −(m2 + p2))): two additions and two fused operations, the same IEEE
+// sequence on host and device. The 1/12 lives in the update coefficient (Coeffs::lam = τ²/(12h²) for order 4), so
+// leapfrog / first_step take d4sum as they take d2sum. The axes are combined as d2sum / d2sum_box combine theirs; with
+// ry = rz = 1 the box form rounds as the cube form does. A neighbour at distance 2 that lies outside the domain (the
+// centre is node 1 or N − 1 of that axis) is the odd reflection u_{−1} = −u_1, u_{N+1} = −u_{N−1}: the caller passes
+// −c for it, never a loaded value.
+W3D_HD double d4axis(double c, double m2, double m1, double p1, double p2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fma(16.0, m1 + p1, __builtin_fma(-30.0, c, -(m2 + p2)));
+#else
+  return std::fma(16.0, m1 + p1, std::fma(-30.0, c, -(m2 + p2)));
+#endif
+}
+template <bool BOX>
+W3D_HD double d4sum_t(double c, double xmm, double xm, double xp, double xpp, double ymm, double ym, double yp, double ypp,
+                      double zmm, double zm, double zp, double zpp, double ry, double rz) {
+  const double dx = d4axis(c, xmm, xm, xp, xpp), dy = d4axis(c, ymm, ym, yp, ypp), dz = d4axis(c, zmm, zm, zp, zpp);
+  if constexpr (BOX) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fma(rz, dz, __builtin_fma(ry, dy, dx));
+#else
+    return std::fma(rz, dz, std::fma(ry, dy, dx));
+#endif
+  } else {
+    return (dx + dy) + dz;
+  }
+}
+
 // Leapfrog update u^{n+1} = 2u^n − u^{n−1} + τ² Δ_h u^n (report.pdf p.5 §2.2(3)), with s = d2sum and lam = τ²/h².
 // The τ²-term is fused: (2c − old) + lam·s rounded once (one v_fma_f64: 10 instead of 11 f64 operations per node and
 // step). Host and device round identically (std::fma is the IEEE fused operation); the printed 128³ / 512³ logs keep

@@ -139,7 +139,7 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("faces", &Sponge::faces)
       .def_property_readonly("on", &Sponge::on);
   py::class_<Problem>(m, "Problem")
-      .def(py::init([](i64 N, double tau, int K, double L, double Ly, double Lz, const Sponge& sponge) {
+      .def(py::init([](i64 N, double tau, int K, double L, double Ly, double Lz, const Sponge& sponge, int order) {
              Problem p;
              p.N = N;
              p.tau = tau;
@@ -148,12 +148,16 @@ PYBIND11_MODULE(_C, m) {
              p.Ly = Ly;
              p.Lz = Lz;
              p.sponge = sponge;
+             p.order = order;
              p.validate();
              return p;
            }),
            py::arg("N") = 512, py::arg("tau") = 1e-3, py::arg("K") = 20, py::arg("L") = 1.0, py::kw_only(),
-           py::arg("Ly") = 0.0, py::arg("Lz") = 0.0, py::arg("sponge") = Sponge{})
+           py::arg("Ly") = 0.0, py::arg("Lz") = 0.0, py::arg("sponge") = Sponge{}, py::arg("order") = 2)
       .def_readwrite("sponge", &Problem::sponge)
+      .def_readwrite("order", &Problem::order)
+      .def_property_readonly("courant_eff", &Problem::courant_eff)
+      .def_property_readonly("cfl_ok_eff", &Problem::cfl_ok_eff)
       .def("validate", &Problem::validate)
       .def_readwrite("N", &Problem::N)
       .def_readwrite("tau", &Problem::tau)
@@ -190,7 +194,8 @@ PYBIND11_MODULE(_C, m) {
       .def_readonly("half_lam", &Coeffs::half_lam)
       .def_readonly("ry", &Coeffs::ry)
       .def_readonly("rz", &Coeffs::rz)
-      .def_readonly("box", &Coeffs::box);
+      .def_readonly("box", &Coeffs::box)
+      .def_readonly("order", &Coeffs::order);
 
   m.def("sin_table_ext", [](const Problem& p) {
     auto v = sin_table_ext(p);
@@ -706,6 +711,22 @@ PYBIND11_MODULE(_C, m) {
         py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("old"), py::arg("boxes"), py::arg("s"),
         py::arg("ct"), py::arg("partials"), py::arg("tiling"), py::arg("stream"), py::arg("sponge") = 0,
         py::arg("lamf") = 0);
+  m.def("gpu_leapfrog4_ty", &leapfrog4_ty, py::arg("tiling"), "tile rows of k_leapfrog4 for this tiling (8 or 16)");
+  m.def("gpu_leapfrog4_blocks",
+        [](const Layout& l, const std::vector<LBox>& boxes, const LeapfrogTiling& t, int min_chunk) {
+          return leapfrog4_blocks(l, boxes.data(), static_cast<int>(boxes.size()), t, min_chunk);
+        },
+        py::arg("layout"), py::arg("boxes"), py::arg("tiling"), py::arg("min_chunk") = 16);
+  m.def("gpu_leapfrog4",
+        [](const Layout& l, const Coeffs& c, std::uintptr_t cur, std::uintptr_t old, const std::vector<LBox>& boxes,
+           std::uintptr_t s, double ct, std::uintptr_t partials, const LeapfrogTiling& t, std::uintptr_t stream,
+           int min_chunk) {
+          launch_leapfrog4(l, c, dptr<const double>(cur), dptr<double>(old), boxes.data(), static_cast<int>(boxes.size()),
+                           dptr<const double>(s) + 1, ct, dptr<Partial>(partials), t, sptr(stream), min_chunk);
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("old"), py::arg("boxes"), py::arg("s"),
+        py::arg("ct"), py::arg("partials"), py::arg("tiling"), py::arg("stream"), py::arg("min_chunk") = 16,
+        "k_leapfrog4: the fourth-order single step (coeffs of an order = 4 problem)");
   m.def("gpu_leapfrog_speed_supported", &leapfrog_speed_supported, py::arg("tiling"), py::arg("sponge"));
   m.def("gpu_sponge_box",
         [](const Layout& l, const Coeffs& c, std::uintptr_t tables, std::uintptr_t prev, std::uintptr_t cur,

@@ -20,6 +20,7 @@ int cpu_set_threads(int n) {
 int cpu_max_threads() { return omp_get_max_threads(); }
 
 void cpu_init_first(const Layout& l, const Coeffs& c, const double* s, double* u0, double* u1) {
+  W3D_REQUIRE(c.order == 2, "order: the analytic start is the second-order one; order 4 starts through cpu_first_step_field");
   const i64 N = l.N;
 #pragma omp parallel for schedule(static)
   for (i64 ix = -1; ix <= l.nx; ++ix) {
@@ -100,8 +101,17 @@ void cpu_first_step_field(const Layout& l, const Layout& src, const Coeffs& c, d
         const double v = f[0];
         u0[o] = v;
         if (gx > 0 && gx < N && gy > 0 && gy < N && gz > 0 && gz < N) {
-          const double lap = c.box ? d2sum_box(v, f[-P], f[P], f[-R], f[R], f[-1], f[1], c.ry, c.rz)
-                                   : d2sum(v, f[-P], f[P], f[-R], f[R], f[-1], f[1]);
+          double lap;
+          if (c.order == 4) {  // (a neighbour at distance 2 outside the domain: the odd reflection −v, not a load)
+            const double xmm = gx == 1 ? -v : f[-2 * P], xpp = gx == N - 1 ? -v : f[2 * P];
+            const double ymm = gy == 1 ? -v : f[-2 * R], ypp = gy == N - 1 ? -v : f[2 * R];
+            const double zmm = gz == 1 ? -v : f[-2], zpp = gz == N - 1 ? -v : f[2];
+            lap = c.box ? d4sum_t<true>(v, xmm, f[-P], f[P], xpp, ymm, f[-R], f[R], ypp, zmm, f[-1], f[1], zpp, c.ry, c.rz)
+                        : d4sum_t<false>(v, xmm, f[-P], f[P], xpp, ymm, f[-R], f[R], ypp, zmm, f[-1], f[1], zpp, c.ry, c.rz);
+          } else {
+            lap = c.box ? d2sum_box(v, f[-P], f[P], f[-R], f[R], f[-1], f[1], c.ry, c.rz)
+                        : d2sum(v, f[-P], f[P], f[-R], f[R], f[-1], f[1]);
+          }
           double w = first_step(v, lap, lamf ? 0.5 * lamf[o] : c.half_lam);
           if (psi) w = first_step_psi(w, psi[src.off(ix, iy, iz)], tau);
           u1[o] = w;
@@ -199,6 +209,51 @@ void leapfrog_impl(const Layout& l, const Coeffs& c, const double* cur, double* 
   }
 }
 
+// Order 4 (stencil.hpp d4sum_t): the same loops with the 13-point operator. The layout spans the whole domain (one
+// ghost layer), so a neighbour at distance 2 is a stored node unless the centre is node 1 or N − 1 of that axis; there
+// it is the odd reflection −u and nothing is read.
+template <bool CHECK, bool BOX>
+void leapfrog4_impl(const Layout& l, const Coeffs& c, const double* cur, double* out, const LBox& b, const double* s,
+                    double ct, ErrAcc* acc) {
+  const i64 nxp = b.x1 - b.x0;
+  std::vector<ErrAcc> part(CHECK ? static_cast<size_t>(nxp) : 0);
+  const i64 P = l.plane, R = l.pitch, N = l.N;
+#pragma omp parallel for schedule(static)
+  for (i64 ix = b.x0; ix < b.x1; ++ix) {
+    double emax = 0.0, esum = 0.0;
+    const double sx = s[l.gx0 + ix];
+    const bool xlo = l.gx0 + ix == 1, xhi = l.gx0 + ix == N - 1;
+    for (i64 iy = b.y0; iy < b.y1; ++iy) {
+      const double sxy = analytic_row(sx, s[l.gy0 + iy], ct);
+      const bool ylo = l.gy0 + iy == 1, yhi = l.gy0 + iy == N - 1;
+      const i64 row = l.off(ix, iy, 0);
+      const double* cr = cur + row;
+      double* orow = out + row;
+      for (i64 iz = b.z0; iz < b.z1; ++iz) {
+        const double u = cr[iz];
+        const bool zlo = l.gz0 + iz == 1, zhi = l.gz0 + iz == N - 1;
+        const double lap = d4sum_t<BOX>(u, xlo ? -u : cr[iz - 2 * P], cr[iz - P], cr[iz + P], xhi ? -u : cr[iz + 2 * P],
+                                        ylo ? -u : cr[iz - 2 * R], cr[iz - R], cr[iz + R], yhi ? -u : cr[iz + 2 * R],
+                                        zlo ? -u : cr[iz - 2], cr[iz - 1], cr[iz + 1], zhi ? -u : cr[iz + 2], c.ry, c.rz);
+        const double v = leapfrog(u, orow[iz], lap, c.lam);
+        orow[iz] = v;
+        if (CHECK) {
+          const double e = std::fabs(v - sxy * s[l.gz0 + iz]);
+          emax = e > emax ? e : emax;
+          esum = err_sq_acc(e, esum);
+        }
+      }
+    }
+    if (CHECK) part[static_cast<size_t>(ix - b.x0)] = ErrAcc{emax, esum};
+  }
+  if (CHECK) {
+    for (const auto& p : part) {
+      acc->max = p.max > acc->max ? p.max : acc->max;
+      acc->sum += p.sum;
+    }
+  }
+}
+
 }  // namespace
 
 namespace {
@@ -216,6 +271,21 @@ void leapfrog_varc(const Layout& l, const Coeffs& c, const double* cur, double* 
 void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* old_out, const LBox& box,
                   const double* s, double ct, ErrAcc* acc, const SpongeView* sponge, const double* lamf) {
   if (box.empty()) return;
+  if (c.order == 4) {
+    W3D_REQUIRE(!sponge && !lamf, "order: no sponge and no speed field with order = 4");
+    W3D_REQUIRE(l.nx == l.N + 1 && l.ny == l.N + 1 && l.nz == l.N + 1, "order: order = 4 needs a layout that spans the domain");
+    if (c.box) {
+      if (acc)
+        leapfrog4_impl<true, true>(l, c, cur, old_out, box, s, ct, acc);
+      else
+        leapfrog4_impl<false, true>(l, c, cur, old_out, box, s, ct, nullptr);
+    } else if (acc) {
+      leapfrog4_impl<true, false>(l, c, cur, old_out, box, s, ct, acc);
+    } else {
+      leapfrog4_impl<false, false>(l, c, cur, old_out, box, s, ct, nullptr);
+    }
+    return;
+  }
   if (lamf) {
     if (c.box) {
       if (acc)
@@ -295,6 +365,7 @@ void source_response_impl(const Problem& p, const Coeffs& c, const i64 node[3], 
 void cpu_source_response(const Problem& p, const Coeffs& c, const i64 node[3], const double* a, bool first_is_start, int s,
                          double* out_last, double* out_prev) {
   W3D_REQUIRE(s >= 1 && s <= kSourceMaxSteps, "source_response: 1..5 steps");
+  W3D_REQUIRE(c.order == 2 || s == 1, "order: with order = 4 the source response is that of a single step");
   W3D_REQUIRE(!first_is_start || s == 1, "source_response: the start is one step");
   W3D_REQUIRE(node[0] > 0 && node[0] < p.N && node[1] > 0 && node[1] < p.N && node[2] > 0 && node[2] < p.N,
               "source_response: the node is not strictly inside the grid");

@@ -113,6 +113,8 @@ void speed_cfl(const Problem& p, const SpeedRange& r, bool force) {
 }
 
 void CpuSolver::set_speed(const double* c, bool force) {
+  W3D_REQUIRE(!c || prob_.order == 2, "order: no speed field with order = 4 (the coefficient form of the fourth-order "
+                                      "operator is a follow-up)");
   if (!c) {
     lamf_.clear();
     c2_.clear();
@@ -148,6 +150,7 @@ void CpuSolver::set_initial(const double* phi, const double* psi) {
 
 EnergySums CpuSolver::energy_sums(int which) const {
   W3D_REQUIRE(which == 0 || which == 1, "energy: which is 0 (E at K-1/2) or 1 (E at 1/2)");
+  W3D_REQUIRE(prob_.order == 2, "order: the second-order discrete energy is not the conserved quantity of the order = 4 scheme");
   W3D_REQUIRE(runs_ > 0, "energy: no solve has run yet");
   if (which == 1) {
     W3D_REQUIRE(initial_ || speed(), "energy: E(1/2) is kept by solves that start from set_initial");
@@ -162,6 +165,7 @@ double CpuSolver::energy(int which) const {
 }
 
 void CpuSolver::set_state(const double* prev, const double* cur, int n0) {
+  W3D_REQUIRE(prob_.order == 2, "order: not together with set_state / --resume");
   W3D_REQUIRE(n0 >= 1 && n0 < prob_.K, "resume step must be in [1, K)");
   W3D_REQUIRE(src_off_.empty(), "sources: not together with set_state (a resumed solve has no step 0 to start the "
                                 "wavelet from)");
@@ -251,7 +255,12 @@ CpuResult CpuSolver::run() {
   } else if (initial_) {
     cpu_first_step_field(lay_, init_lay_, c, prob_.tau, init_[0].data(), init_[1].empty() ? nullptr : init_[1].data(),
                          u_[0].data(), u_[1].data(), lamf);
-    e_start_ = cpu_energy(lay_, c, prob_.tau, u_[0].data(), u_[1].data(), lamf ? c2_.data() : nullptr);
+    if (prob_.order == 2) e_start_ = cpu_energy(lay_, c, prob_.tau, u_[0].data(), u_[1].data(), lamf ? c2_.data() : nullptr);
+  } else if (prob_.order == 4) {
+    // order 4 without set_initial: the eigenmode array through the first-step-field path, as a speed solve starts
+    const Layout il = initial_layout(prob_, lay_);
+    std::vector<double> phi0 = eigenmode_local(prob_, il);
+    cpu_first_step_field(lay_, il, c, prob_.tau, phi0.data(), nullptr, u_[0].data(), u_[1].data(), nullptr);
   } else if (lamf) {
     // a speed field without set_initial: the eigenmode array through the first-step-field path (u⁰ is cpu_init_first's)
     const Layout il = initial_layout(prob_, lay_);

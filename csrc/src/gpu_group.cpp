@@ -10,6 +10,8 @@ namespace wave3d {
 GpuGroup::GpuGroup(const Problem& prob, const SolverOptions& opt, int world, const std::string& transport)
     : transport_(transport) {
   W3D_REQUIRE(world >= 1, "world must be >= 1");
+  W3D_REQUIRE(prob.order == 2, "order: order = 4 runs on one GPU rank only, not in a GpuGroup (the stencil needs ghosts two "
+                               "deep per step)");
   W3D_REQUIRE(transport == "loopback" || transport == "rccl-self" || transport == "push" || transport == "sdma" ||
                   transport == "multi-device",
               "group transport must be loopback, rccl-self, push, sdma or multi-device, not " + transport);

@@ -54,7 +54,10 @@ struct FirstStepParams {
 // rz. For a cube Coeffs::from fills ry = rz = 1.0, and the box form fed ratios of 1 rounds exactly as d2sum does
 // (stencil.hpp), so the cube's bits depend on those two fields being 1.0 — as in k_init_first.
 // VARC: a speed field — the coefficient of a node is 0.5·lamf[p] (exact), the pair loaded at the thread's store offset.
-template <bool VARC>
+// ORDER4: the fourth-order operator (stencil.hpp d4sum_t). The x∓2 / y∓2 pairs and the pairs left and right are loaded
+// only where the node they serve is not next to that wall; there the neighbour is −centre. Every address read belongs to
+// a node of the global grid within two layers of an interior node, which the source layout (ghost depth ≥ 2) holds.
+template <bool VARC, bool ORDER4 = false>
 __global__ __launch_bounds__(256) void k_first_step_field(const FirstStepParams p) {
   const int q = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
   if (q >= p.pairs_per_plane) return;
@@ -93,6 +96,24 @@ __global__ __launch_bounds__(256) void k_first_step_field(const FirstStepParams 
         hl.x = 0.5 * lf.x;
         hl.y = 0.5 * lf.y;
       }
+      if constexpr (ORDER4) {
+        const i64 N = p.N, gz0 = p.gz0 + iz0, gz1 = gz0 + 1;
+        v2d ncv;
+        ncv.x = -cv.x;
+        ncv.y = -cv.y;
+        const v2d x2m = gx == 1 ? ncv : ld2(f - 2 * p.s_plane), x2p = gx == N - 1 ? ncv : ld2(f + 2 * p.s_plane);
+        const v2d y2m = gy == 1 ? ncv : ld2(f - 2 * p.s_pitch), y2p = gy == N - 1 ? ncv : ld2(f + 2 * p.s_pitch);
+        if (in[0]) {
+          const double zm = f[-1], z2m = gz0 == 1 ? ncv.x : f[-2], z2p = gz0 == N - 1 ? ncv.x : f[2];
+          a[0] = first_step(cv.x, d4sum_t<true>(cv.x, x2m.x, xm.x, xp.x, x2p.x, y2m.x, ym.x, yp.x, y2p.x, z2m, zm, cv.y, z2p,
+                                                p.ry, p.rz), hl.x);
+        }
+        if (in[1]) {
+          const double zp = f[2], z2m = gz1 == 1 ? ncv.y : f[-1], z2p = gz1 == N - 1 ? ncv.y : f[3];
+          a[1] = first_step(cv.y, d4sum_t<true>(cv.y, x2m.y, xm.y, xp.y, x2p.y, y2m.y, ym.y, yp.y, y2p.y, z2m, cv.x, zp, z2p,
+                                                p.ry, p.rz), hl.y);
+        }
+      } else {
       if (in[0]) {
         const double zm = f[-1];
         a[0] = first_step(cv.x, d2sum_box(cv.x, xm.x, xp.x, ym.x, yp.x, zm, cv.y, p.ry, p.rz), hl.x);
@@ -100,6 +121,7 @@ __global__ __launch_bounds__(256) void k_first_step_field(const FirstStepParams 
       if (in[1]) {
         const double zp = f[2];
         a[1] = first_step(cv.y, d2sum_box(cv.y, xm.y, xp.y, ym.y, yp.y, cv.x, zp, p.ry, p.rz), hl.y);
+      }
       }
       if (p.psi) {
         const v2d sv = ld2(p.psi + so);
@@ -293,7 +315,12 @@ void launch_first_step_field(const Layout& l, const Layout& src, const Coeffs& c
   p.tau = tau;
   p.lamf = lamf;
   const dim3 grid(static_cast<unsigned>(ceil_div(p.pairs_per_plane, 256)), static_cast<unsigned>(l.nx + 2 * l.xg));
-  if (lamf)
+  if (c.order == 4) {
+    W3D_REQUIRE(!lamf, "order: no speed field with order = 4");
+    W3D_REQUIRE(l.nx == l.N + 1 && l.ny == l.N + 1 && l.nz == l.N + 1, "order: the fourth-order first step needs one rank's "
+                                                                     "layout that spans the whole domain");
+    hipLaunchKernelGGL((k_first_step_field<false, true>), grid, dim3(256), 0, stream, p);
+  } else if (lamf)
     hipLaunchKernelGGL(k_first_step_field<true>, grid, dim3(256), 0, stream, p);
   else
     hipLaunchKernelGGL(k_first_step_field<false>, grid, dim3(256), 0, stream, p);

@@ -33,6 +33,8 @@ void write_dump(const std::string& prefix, const Problem& p, const Layout& l, co
     j << ", \"sponge\": [" << p.sponge.width << ", " << p.sponge.sigma << ", " << p.sponge.faces << "]";
   // (a speed field: the interior minimum and maximum of c; absent without one)
   if (speed) j << ", \"speed\": [" << speed->cmin << ", " << speed->cmax << "]";
+  // (the spatial order, when it is not 2 — "order" is the array's memory order here; absent for order 2)
+  if (p.order != 2) j << ", \"space_order\": " << p.order;
   j << ", \"tau\": " << p.tau << ", \"step\": " << step << ", \"t\": " << step * p.tau
     << ", \"shape\": [" << l.nx << ", " << l.ny << ", " << l.nz << "], \"offset\": [" << l.gx0 << ", " << l.gy0
     << ", " << l.gz0 << "], \"global_shape\": [" << p.N + 1 << ", " << p.N + 1 << ", " << p.N + 1
@@ -160,6 +162,7 @@ void write_traces(const std::string& out, const Problem& p, const std::vector<i6
   j << "{\"format\": \"wave3d-traces-v1\", \"dtype\": \"float64\", \"order\": \"C\", \"N\": " << p.N << ", \"K\": " << p.K
     << ", \"L\": " << p.L;
   if (p.is_box()) j << ", \"box\": [" << p.L << ", " << p.edge_y() << ", " << p.edge_z() << "]";
+  if (p.order != 2) j << ", \"space_order\": " << p.order;
   j << ", \"tau\": " << p.tau << ", \"shape\": [" << rows << ", " << R << "], \"nodes\": [";
   for (size_t r = 0; r < R; ++r)
     j << (r ? ", [" : "[") << ijk[3 * r] << ", " << ijk[3 * r + 1] << ", " << ijk[3 * r + 2] << "]";

@@ -275,6 +275,16 @@ std::vector<UnitPlan> plan_units(const RankSchedule& s, int start_n, bool analyt
   int n = start_n;
   const bool varc = speed != SpeedPlan::kNone;
   W3D_REQUIRE(!varc || (s.world == 1 && !analytic), "speed: one rank and a stored start only");
+  if (s.prob.order == 4) {
+    // the fourth-order operator has single steps only (k_leapfrog4), whatever temporal and tb say: no analytic-start
+    // pass, no exchange, no drop_prev
+    W3D_REQUIRE(s.world == 1 && !analytic && !varc, "order: one rank, a stored start and no speed field only");
+    for (; n <= K - 1; ++n) {
+      units.push_back(UnitPlan{n, 1});
+      units.back().interior = s.full;
+    }
+    return units;
+  }
   if (speed == SpeedPlan::kFused && !speed_fused_ok(s)) speed = SpeedPlan::kPairs;  // (e.g. a box the pass does not take)
   if (speed == SpeedPlan::kFused) {
     // the split of a stored start by the coefficient passes' own measured costs, no deeper than they are built

@@ -49,6 +49,12 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
     W3D_REQUIRE(o.temporal < 2 || o.tb,
                 "sponge: tb = false runs k_leapfrog2 pairs, which have no damped form; use the LDS passes or temporal = 1");
   }
+  if (prob.order == 4) {  // (the fourth-order operator: solver.hpp order4())
+    W3D_REQUIRE(world == 1 && !loopback_, "order: order = 4 runs on one GPU rank only (no GpuGroup, RCCL ranks, --np or "
+                                          "runtime=\"process\": the stencil needs ghosts two deep per step)");
+    W3D_REQUIRE(!o.fake_comm, "order: not on a fake rank");
+    W3D_REQUIRE(!o.push && !o.sdma, "order: not on the push or copy-engine transports");
+  }
   // (the push transport's kernels exist for cubes only: kernels_leapfrog_tb_push.hip)
   W3D_REQUIRE(!(o.push && world > 1 && coef_.box),
               "the push transport has no rectangular-box kernels: run a --box problem over rccl or sdma");
@@ -148,7 +154,8 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
   }
   n_dint_ = sch_.dint.empty() ? 0 : leapfrog2_partials(sch_.lay, sch_.dint, sch_.opt.tiling2);
   n_deep += n_dint_;
-  n_partials_ = std::max({n_full_, n_shell_ + n_int_, error_blocks(sch_.lay, sch_.full), n_fused_, n_deep,
+  if (order4()) n_full4_ = leapfrog4_blocks(sch_.lay, &sch_.full, 1, sch_.opt.tiling);
+  n_partials_ = std::max({n_full_, n_full4_, n_shell_ + n_int_, error_blocks(sch_.lay, sch_.full), n_fused_, n_deep,
                           sch_.opt.init2 ? init_two_partials(sch_.lay) : 0, 1});
   W3D_HIP(hipMalloc(&partials_, static_cast<size_t>(n_partials_) * sizeof(Partial)));
   // the LDS passes' partials live apart: their reductions are deferred, so the immediate users of partials_ (init,
@@ -174,9 +181,17 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
     sponge_box_prepare();  // (the dynamic-LDS limit: before any capture)
     for (int st = 2; st <= 5; ++st) sponge_boxes_[st] = sponge_boxes(sch_.prob, sch_.lay, st);
   }
+  if (order4()) {  // no analytic start: the eigenmode array through the first-step-field path until set_initial replaces it
+    init_lay_ = initial_layout(sch_.prob, sch_.lay);
+    const std::vector<double> phi0 = eigenmode_local(sch_.prob, init_lay_);
+    W3D_HIP(hipMalloc(&init_[0], static_cast<size_t>(init_lay_.bytes())));
+    W3D_HIP(hipMemcpy(init_[0], phi0.data(), static_cast<size_t>(init_lay_.bytes()), hipMemcpyHostToDevice));
+  }
 }
 
 void GpuSolver::set_speed(const double* c, bool force) {
+  W3D_REQUIRE(!c || !order4(), "order: no speed field with order = 4 (the coefficient form of the fourth-order operator is "
+                               "a follow-up)");
   DeviceScope scope(dev_, true);
   if (!c) {
     if (!speed()) return;
@@ -347,7 +362,7 @@ void GpuSolver::set_initial(const double* phi, const double* psi) {
     if (!init_[k]) W3D_HIP(hipMalloc(&init_[k], bytes));
     W3D_HIP(hipMemcpy(init_[k], host.data(), bytes, hipMemcpyHostToDevice));
   }
-  if (sch_.world == 1) energy_alloc();
+  if (sch_.world == 1 && !order4()) energy_alloc();
   speed_eig_ = false;  // (init_[0] is the caller's φ now)
   initial_ = true;
   initial_runs_ = 0;
@@ -455,6 +470,7 @@ void GpuSolver::source_correct(const UnitPlan* u, double* prev, double* last) {
 Partial GpuSolver::energy_sums(int which) const {
   W3D_REQUIRE(sch_.world == 1, "energy: one rank only (multi-rank: Solver.energy assembles the global fields)");
   W3D_REQUIRE(which == 0 || which == 1, "energy: which is 0 (E at K-1/2) or 1 (E at 1/2)");
+  W3D_REQUIRE(!order4(), "order: the second-order discrete energy is not the conserved quantity of the order = 4 scheme");
   W3D_REQUIRE(!speed(), "speed: k_energy has no mass weight 1/c^2; Solver.energy downloads both levels and runs cpu_energy");
   W3D_REQUIRE(runs_ > 0 && (!initial_ || initial_runs_ > 0), "energy: no solve has run yet");
   W3D_REQUIRE(which == 0 || initial_, "energy: E(1/2) is kept by solves that start from set_initial");
@@ -482,6 +498,7 @@ void GpuSolver::set_state(const double* prev, const double* cur, int n0) {
   W3D_REQUIRE(sch_.mode != Mode::kDeep || (sch_.prob.K - n0) % 2 == 0, "resume: two-step passes need an even step count left");
   W3D_REQUIRE(n_src_ == 0, "sources: not together with set_state (a resumed solve has no step 0 to start the wavelet from)");
   W3D_REQUIRE(!speed(), "speed: not together with set_state / --resume");
+  W3D_REQUIRE(!order4(), "order: not together with set_state / --resume");
   if (initial_) {  // (the two starts replace each other)
     W3D_HIP(hipDeviceSynchronize());
     for (double*& p : init_) {
@@ -543,7 +560,7 @@ void GpuSolver::phase_init() {
     W3D_HIP(hipMemsetAsync(trace_, 0xFF, static_cast<size_t>(K + 1) * recv_.size() * sizeof(double), s0_));
   // one rank on the LDS kernel: the first pass starts from the analytic u⁰, u¹ itself (no init kernel, no reads)
   analytic_ = (sch_.mode == Mode::kFusedSingle || sch_.mode == Mode::kDeepTb) && sch_.analytic_ok() && resume_n_ == 0 &&
-              !initial_ && !recording_ && n_src_ == 0 && !sponge() && !speed();  // (receivers: both start levels are stored, rows 0
+              !initial_ && !recording_ && n_src_ == 0 && !sponge() && !speed() && !order4();  // (receivers: both start levels are stored, rows 0
                                                         // and 1 are gathered; sources: u¹ is corrected in memory;
                                                         // sponge layers: the start is stored, as with receivers)
   if (resume_n_ > 0) {  // loaded state: u^{n0−1} → buf 0, u^{n0} → buf 1 (ghosts included)
@@ -553,13 +570,14 @@ void GpuSolver::phase_init() {
       W3D_HIP(hipMemcpyAsync(u_[1], resume_[1].data(), bytes, hipMemcpyHostToDevice, s0_));
     });
     start_n_ = resume_n_;
-  } else if (initial_ || speed()) {  // user-supplied φ, ψ: u⁰ → buf 0, u¹ → buf 1 (ghosts included) from the device-resident copies
-    // (a speed field without set_initial: init_[0] is the eigenmode array, init_[1] null; the coefficient per node)
+  } else if (initial_ || speed() || order4()) {  // user-supplied φ, ψ: u⁰ → buf 0, u¹ → buf 1 (ghosts included) from the device-resident copies
+    // (a speed field without set_initial: init_[0] is the eigenmode array, init_[1] null; the coefficient per node.
+    // order 4 without set_initial likewise; its coefficients select the kernel's fourth-order form)
     timed(kPhaseInit, s0_, [&] {
       launch_first_step_field(sch_.lay, init_lay_, coef_, sch_.prob.tau, init_[0], init_[1], u_[0], u_[1], s0_, lamf_dev_);
     });
     timed(kPhaseCheck, s0_, [&] {
-      if (energy_part_ && sch_.world == 1 && !speed()) {  // E^{1/2}, kept in its device slot
+      if (energy_part_ && sch_.world == 1 && !speed() && !order4()) {  // E^{1/2}, kept in its device slot
         const int ne = energy_partials(sch_.lay);
         launch_energy(sch_.lay, coef_, sch_.prob.tau, u_[0], u_[1], energy_part_, s0_);
         launch_energy_reduce(energy_part_, ne, energy_part_ + ne + 1, s0_);
@@ -819,7 +837,12 @@ void GpuSolver::unit_interior(int i) {
   const bool wait = needs_exchange(i) && xstream() != s0_ && (!loopback_ || sch_.sdma);
   int np = 0;  // partials to reduce
   bool joined = false;
-  if (sch_.mode == Mode::kDeep) {
+  if (order4()) {  // (single steps only: plan_units; one rank, so no shell preceded it)
+    timed(kPhaseCompute, s0_, [&] {
+      launch_leapfrog4(sch_.lay, coef_, u_[cur_], u_[old_], &sch_.full, 1, s, ct, chk ? partials_ : nullptr, sch_.opt.tiling, s0_);
+    });
+    np = n_full4_;
+  } else if (sch_.mode == Mode::kDeep) {
     int off = 0;
     for (int n : n_dshell_) off += n;
     if (!sch_.dint.empty()) {

@@ -71,6 +71,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "format; face values ignored, interior values finite and > 0; courant * max c <= 1 unless "
                          "--force); one rank, backends hip (temporal 1 or 2) and cpu; not with --resume; the error lines "
                          "then have no meaning")
+    ap.add_argument("--order", type=int, default=2, choices=(2, 4),
+                    help="spatial order of the Laplacian (default 2). 4: the 13-point stencil with the odd reflection at the "
+                         "walls, stable for courant <= sqrt(3)/2; one native rank (hip or cpu); not with --sponge, --speed, "
+                         "--resume or --energy")
     ap.add_argument("--force", action="store_true", help="run even if the CFL condition is violated")
     ap.add_argument("--quiet", action="store_true")
     return ap
@@ -98,6 +102,8 @@ def main(argv=None) -> int:
         ap.error("--energy needs --initial (E(1/2) is kept by solves that start from it)")
     if a.sources and a.resume:
         ap.error("--sources and --resume exclude each other")
+    if a.order == 4 and (a.resume or a.speed or a.sponge or a.energy):
+        ap.error("order: --order 4 not together with --resume, --speed, --sponge or --energy")
     if a.speed and a.resume:
         ap.error("speed: not together with --resume")
     if bool(a.receivers) != bool(a.traces):
@@ -126,12 +132,17 @@ def main(argv=None) -> int:
     from .utils.report import gcell_per_s
 
     spec = ProblemSpec(N=a.N, tau=a.tau, K=a.K, L=a.L, check_every=a.check_every,
-                       Ly=box[1] if box else None, Lz=box[2] if box else None, sponge=sponge)
+                       Ly=box[1] if box else None, Lz=box[2] if box else None, sponge=sponge, order=a.order)
     if spec.sponge is not None:
         print("wave3d: sponge layers are set: the error columns compare with the undamped eigenmode and have no meaning",
               file=sys.stderr)
     box_note = " box=" + ",".join(f"{e:g}" for e in spec.edges) if spec.is_box else ""
-    if not spec.cfl_ok:
+    if spec.order == 4 and not spec.cfl_ok:
+        print(f"wave3d: CFL violated: courant = {spec.courant:.4f} > sqrt(3)/2 for --order 4 (effective "
+              f"{spec.courant_eff:.4f} > 1, tau_max = {spec.tau_max * math.sqrt(3.0) / 2.0:.3e})", file=sys.stderr)
+        if not a.force:
+            return 2
+    elif not spec.cfl_ok:
         form = "tau*sqrt(1/hx^2+1/hy^2+1/hz^2)" if spec.is_box else "tau*sqrt(3)/h"
         print(f"wave3d: CFL violated: courant = {form} = {spec.courant:.4f} > 1 (tau_max = {spec.tau_max:.3e}"
               f"{' for' + box_note if box_note else ''})", file=sys.stderr)
@@ -252,13 +263,17 @@ def main(argv=None) -> int:
                            **({"sources": n_sources} if a.sources else {}),
                            **({"sponge": list(spec.sponge)} if spec.sponge is not None else {}),
                            **({"speed": speed_range} if speed_range is not None else {}),
+                           **({"order": spec.order} if spec.order != 2 else {}),
                            "steps": [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]}, f)
     if a.traces:
-        dumpio.save_traces(a.traces, s.traces().numpy(), nodes, N=a.N, K=a.K, L=a.L, tau=a.tau, box=spec.edges)
+        dumpio.save_traces(a.traces, s.traces().numpy(), nodes, N=a.N, K=a.K, L=a.L, tau=a.tau, box=spec.edges,
+                           extra={"space_order": spec.order} if spec.order != 2 else None)
     if a.dump or a.checkpoint:
         sponge_meta = {"sponge": list(spec.sponge)} if spec.sponge is not None else None  # (absent without a sponge)
         if speed_range is not None:  # (... and a speed field only when set: the interior minimum and maximum of c)
             sponge_meta = {**(sponge_meta or {}), "speed": speed_range}
+        if spec.order != 2:  # (... and the spatial order only when it is not 2; "order" is the memory order there)
+            sponge_meta = {**(sponge_meta or {}), "space_order": spec.order}
 
         def write(prefix, which):
             if s.transport in ("loopback", "rccl-self", "push", "sdma"):

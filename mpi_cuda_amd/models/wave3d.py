@@ -51,7 +51,11 @@ class ProblemSpec:
     ``sponge = (width, sigma, faces)`` (or just ``width``, or ``(width, sigma)``) puts an absorbing layer of ``width``
     nodes next to the faces of the mask ``faces`` (bits 0..5: x-, x+, y-, y+, z-, z+, or a string of the letters
     ``xXyYzZ``, lower case = low face; default all six) with peak damping rate ``sigma`` (0: the default
-    3 ln(1000) / (2 width h)); CLI ``--sponge W[,SIGMA[,FACES]]``. None, width 0 or faces 0: no sponge."""
+    3 ln(1000) / (2 width h)); CLI ``--sponge W[,SIGMA[,FACES]]``. None, width 0 or faces 0: no sponge.
+
+    ``order`` is the spatial order of the Laplacian: 2 (the 7-point stencil) or 4 (the 13-point one with the odd
+    reflection u_{-1} = -u_1 at the Dirichlet walls; CLI ``--order 4``). Order 4 is stable for
+    tau sqrt(sum 1/h_d^2) <= sqrt(3)/2 (``courant_eff``) and runs on one native rank, without a sponge."""
 
     N: int = 512
     tau: float = 1e-3
@@ -62,8 +66,11 @@ class ProblemSpec:
     Ly: float | None = None
     Lz: float | None = None
     sponge: tuple | int | None = None
+    order: int = 2
 
     def __post_init__(self) -> None:
+        if self.order not in (2, 4):
+            raise ValueError("order: the spatial order must be 2 or 4")
         if self.sponge is not None:
             sp = self.sponge if isinstance(self.sponge, (tuple, list)) else (self.sponge,)
             if not 1 <= len(sp) <= 3:
@@ -88,6 +95,9 @@ class ProblemSpec:
                 raise ValueError(f"sponge: two layers of width {width} do not fit into the {self.N - 1} interior nodes "
                                  "of an axis (2 * width <= N - 1)")
             self.sponge = (width, sigma, faces) if width > 0 and faces else None
+        if self.order == 4 and self.sponge is not None:
+            raise ValueError("order: no sponge layers with order = 4 (the damped form of the fourth-order operator is a "
+                             "follow-up)")
         if self.N < 2:
             raise ValueError("N must be >= 2")
         if not (self.tau > 0 and math.isfinite(self.tau)):
@@ -151,8 +161,14 @@ class ProblemSpec:
         return self.tau * math.sqrt(3.0) / self.h
 
     @property
+    def courant_eff(self) -> float:
+        """The order-aware Courant number: courant·2/√3 for order 4 (the largest symbol of −h²D₄ is 16/3 against 4), courant
+        itself for order 2 (problem.hpp::Problem::courant_eff)."""
+        return self.courant * (2.0 / math.sqrt(3.0)) if self.order == 4 else self.courant
+
+    @property
     def cfl_ok(self) -> bool:
-        return self.courant <= 1.0
+        return self.courant_eff <= 1.0
 
     @property
     def tau_max(self) -> float:
@@ -174,6 +190,8 @@ class ProblemSpec:
 
         C = load()
         kw = {} if self.sponge is None else {"sponge": C.Sponge(*self.sponge)}
+        if self.order != 2:
+            kw["order"] = self.order
         if self.Ly is None and self.Lz is None:
             return C.Problem(self.N, self.tau, self.K, self.L, **kw)
         _, ly, lz = self.edges
@@ -187,6 +205,8 @@ class ProblemSpec:
             d.pop("Lz")
         else:
             d["Ly"], d["Lz"] = self.edges[1], self.edges[2]
+        if self.order == 2:  # (... and so is a second-order spec's)
+            d.pop("order")
         if self.sponge is None:  # (... and so is a spec's without a sponge)
             d.pop("sponge")
         else:

@@ -110,6 +110,10 @@ class Solver:
             spec = dataclasses.replace(spec, sponge=sponge)
 
         if not spec.cfl_ok and not force:
+            if spec.order == 4:
+                raise ValueError(f"CFL violated: courant = {spec.courant:.4f} > sqrt(3)/2 for order = 4 (effective "
+                                 f"{spec.courant_eff:.4f} > 1, tau_max = {spec.tau_max * math.sqrt(3.0) / 2.0:.3e}); "
+                                 "pass force=True to run anyway")
             raise ValueError(f"CFL violated: courant = {spec.courant:.4f} > 1 (tau_max = {spec.tau_max:.3e}); "
                              "pass force=True to run anyway")
         if rank is None or world is None:
@@ -133,6 +137,22 @@ class Solver:
             if not tb and temporal >= 2:
                 raise ValueError("sponge: tb=False runs k_leapfrog2 pairs, which have no damped form; use the LDS "
                                  "passes or temporal=1")
+        if spec.order == 4:
+            # one native rank: CpuSolver is the definition, one GpuSolver that spans the domain matches it
+            if runtime == "process":
+                raise ValueError("order: order = 4 not with runtime='process' (one in-process rank only)")
+            if world > 1:
+                raise ValueError("order: order = 4 runs on one rank only (the stencil needs ghosts two deep per step)")
+            if self.backend == "torch" or self.transport == "torch":
+                raise ValueError("order: order = 4 on the native backends only (backend 'hip' with transport 'rccl', or "
+                                 "'cpu')")
+            if self.transport in ("push", "push-ipc", "sdma", "sdma-ipc", "loopback", "rccl-self", "multi-device") \
+                    or copy_engines:
+                raise ValueError("order: order = 4 runs on one GPU rank that spans the domain only (no group, push or "
+                                 "copy-engine transport)")
+            if speed is not None:
+                raise ValueError("order: no speed field with order = 4 (the coefficient form of the fourth-order operator "
+                                 "is a follow-up)")
         self._speed = None  # (set_speed's global c: the hip backend's weighted energy is computed from it on the host)
         self._force = bool(force)
         if speed is not None:
@@ -382,6 +402,8 @@ class Solver:
         fields (no exchange before the first pass); the result is bit-identical to an uninterrupted run."""
         import numpy as np
 
+        if self.spec.order == 4:
+            raise ValueError("order: order = 4 not together with set_state / --resume")
         if self.backend == "torch":
             raise ValueError("the torch reference solver has no resume")
         if self.runtime == "process":
@@ -405,6 +427,9 @@ class Solver:
         columns then mean nothing; ``energy`` carries the mass weight 1/c². Not with ``set_state``."""
         import numpy as np
 
+        if c is not None and self.spec.order == 4:
+            raise ValueError("order: no speed field with order = 4 (the coefficient form of the fourth-order operator is a "
+                             "follow-up)")
         if self.runtime == "process":
             raise ValueError("speed: not with runtime='process' (use bin/wave3d --speed)")
         if self.backend == "torch" or self.transport == "torch" or not hasattr(self._impl, "set_speed"):
@@ -548,6 +573,9 @@ class Solver:
             raise ValueError("runtime='process' has no energy from Python (use bin/wave3d --energy)")
         if self.backend == "torch" or self.transport == "torch":
             raise ValueError("energy needs the native hip or cpu backend")
+        if self.spec.order == 4:
+            raise ValueError("order: the second-order discrete energy is not the conserved quantity of the order = 4 "
+                             "scheme")
         C = load()
         if self._speed is not None and self.backend == "hip":
             # a speed field on the hip backend: both levels on the host, cpu_energy with the mass weight 1/c² (k_energy

@@ -65,7 +65,8 @@ def box_of(meta: dict) -> tuple[float, float, float]:
 TRACES_FORMAT = "wave3d-traces-v1"
 
 
-def save_traces(prefix: str, traces: np.ndarray, nodes, *, N: int, K: int, L: float, tau: float, box=None) -> None:
+def save_traces(prefix: str, traces: np.ndarray, nodes, *, N: int, K: int, L: float, tau: float, box=None,
+                extra: dict | None = None) -> None:
     """Receiver traces (``Solver.traces()``, ``--traces``): ``<prefix>.bin`` raw little-endian float64, C order
     [K+1][R], row n = u^n at the R nodes; ``<prefix>.json`` {"format": "wave3d-traces-v1", "dtype", "order", "N", "K",
     "L" [, "box"], "tau", "shape": [K+1, R], "nodes": [[i, j, k], ...]}. The native CLI writes the same files."""
@@ -78,6 +79,8 @@ def save_traces(prefix: str, traces: np.ndarray, nodes, *, N: int, K: int, L: fl
             "tau": float(tau), "shape": list(traces.shape), "nodes": nodes}
     if box is not None and not (box[0] == box[1] == box[2]):
         meta["box"] = [float(e) for e in box]
+    if extra:  # (keys a solve adds only when set, e.g. "space_order": 4)
+        meta.update(extra)
     with open(prefix + ".json", "w") as f:
         json.dump(meta, f)
 

@@ -46,6 +46,7 @@ CPU_FLAGS = COMMON + ["-fopenmp", "-march=x86-64-v3"]
 # (source, compiler kind). 'hip' = device code or HIP runtime host code, 'cpu' = plain C++ with OpenMP.
 LIB_SOURCES = [
     ("src/kernels_stencil.hip", "hip"),
+    ("src/kernels_stencil4.hip", "hip"),
     ("src/kernels_halo.hip", "hip"),
     ("src/kernels_leapfrog2.hip", "hip"),
     ("src/kernels_init2.hip", "hip"),

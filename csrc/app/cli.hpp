@@ -96,7 +96,7 @@ std::string box_banner(const Problem& p);
 std::string box_json(const Problem& p);
 // sponge layers for the JSON summaries (", \"sponge\": [width, sigma, faces]"); empty without a sponge
 std::string sponge_json(const Problem& p);
-// the spatial order for the JSON summaries (", \"order\": 4"); empty for order 2
+// the spatial and time orders for the JSON summaries (", \"order\": 4", ", \"time_order\": 4"); each absent for 2
 std::string order_json(const Problem& p);
 // --sponge: says once on stderr that the error columns have no meaning (nothing without a sponge)
 void sponge_notice(const Problem& p);

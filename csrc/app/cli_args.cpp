@@ -127,6 +127,9 @@ constexpr Personality kPersonalities[] = {
                "  --order 2|4        spatial order of the Laplacian (default 2). 4: the 13-point stencil with the odd reflection\n"
                "                     u(-1) = -u(1) at the walls; stable for courant <= sqrt(3)/2; one GPU rank (single steps) or\n"
                "                     --cpu; not with --sponge, --speed, --resume, --energy, --np, --group, --serve, --fake-rank\n"
+               "  --time-order 2|4   order of the time integrator (default 2). 4: u^{n+1} = 2u^n - u^{n-1} + tau^2 L u^n +\n"
+               "                     tau^4/12 L^2 u^n; needs --order 4; stable for courant <= 3/2; runs where --order 4 runs;\n"
+               "                     not with --sources\n"
                "  --force            run even if the CFL condition is violated\n"
                "  --quiet            only the summary\n");
   std::exit(2);
@@ -285,6 +288,11 @@ Args parse(int argc, char** argv) {
       if (v != "2" && v != "4") usage("order: --order expects 2 or 4");
       a.prob.order = v == "4" ? 4 : 2;
     }
+    else if (s == "--time-order") {
+      const std::string v = next();
+      if (v != "2" && v != "4") usage("time_order: --time-order expects 2 or 4");
+      a.prob.time_order = v == "4" ? 4 : 2;
+    }
     else if (s == "--quiet") a.quiet = true;
     else if (s == "-h" || s == "--help") usage();
     else if (!s.empty() && s[0] == '-' && s.size() > 1 && !std::isdigit(static_cast<unsigned char>(s[1])) && s[1] != '.')
@@ -324,6 +332,11 @@ Args parse(int argc, char** argv) {
   if (!a.speed.empty() && (a.np > 1 || a.group > 0 || a.serve || a.fake_rank >= 0))
     usage("speed: one rank only (not with --np, --group, --serve or --fake-rank)");
   if (!a.speed.empty() && !a.resume.empty()) usage("speed: not together with --resume");
+  if (a.prob.time_order == 4) {
+    if (a.prob.order != 4) usage("time_order: 4 needs order = 4 (--order 4)");
+    if (a.cpu && a.np > 1) usage("time_order: the distributed CPU program has no time_order = 4 step (one process: --cpu)");
+    if (!a.sources.empty()) usage("time_order: --time-order 4 takes no --sources");
+  }
   if (a.prob.order == 4) {
     if (a.np > 1 || a.group > 0 || a.serve || a.fake_rank >= 0)
       usage("order: --order 4 runs on one rank only (not with --np, --group, --serve or --fake-rank)");
@@ -367,7 +380,10 @@ std::string box_json(const Problem& p) {
   if (!p.is_box()) return "";
   return ", \"box\": [" + jexact(p.L) + ", " + jexact(p.edge_y()) + ", " + jexact(p.edge_z()) + "]";
 }
-std::string order_json(const Problem& p) { return p.order == 2 ? "" : ", \"order\": " + std::to_string(p.order); }
+std::string order_json(const Problem& p) {
+  return (p.order == 2 ? std::string() : ", \"order\": " + std::to_string(p.order)) +
+         (p.time_order == 2 ? std::string() : ", \"time_order\": " + std::to_string(p.time_order));
+}
 std::string sponge_json(const Problem& p) {
   if (!p.sponge.on()) return "";
   return ", \"sponge\": [" + std::to_string(p.sponge.width) + ", " + jexact(p.sponge.sigma) + ", " +

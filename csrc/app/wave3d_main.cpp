@@ -516,7 +516,14 @@ int main(int argc, char** argv) {
   try {
     Args a = parse(argc, argv);
     a.prob.validate();
-    if (a.prob.order == 4 && !a.prob.cfl_ok_eff()) {
+    if (a.prob.time_order == 4 && !a.prob.cfl_ok_eff()) {
+      std::fprintf(stderr,
+                   "wave3d: CFL violated: courant = %.4f > 3/2 for --order 4 --time-order 4 (effective %.4f > 1, tau_max = "
+                   "%.3e for N=%lld); the scheme is unstable.%s\n",
+                   a.prob.courant(), a.prob.courant_eff(), a.prob.tau_max() * 1.5, static_cast<long long>(a.prob.N),
+                   a.force ? " Continuing (--force)." : " Use a smaller tau, or --force.");
+      if (!a.force) return 2;
+    } else if (a.prob.order == 4 && !a.prob.cfl_ok_eff()) {
       std::fprintf(stderr,
                    "wave3d: CFL violated: courant = %.4f > sqrt(3)/2 for --order 4 (effective %.4f > 1, tau_max = %.3e for "
                    "N=%lld); the leapfrog scheme is unstable.%s\n",

@@ -183,6 +183,21 @@ void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* o
                   const double* s, double ct, ErrAcc* acc, const SpongeView* sponge = nullptr,
                   const double* lamf = nullptr);
 
+// Fourth order in time (Coeffs::time_order = 4, which needs order = 4; stencil.hpp leapfrog_t4): a step applies the
+// fourth-order operator twice, through a third field v in the solve layout that spans the domain.
+//   cpu_lap4:        v = lam·s(u) (lap_t4) on the nodes of `box` (inside the global interior); nothing else of v is
+//                    written. The caller keeps v's six faces at exact zeros (a zeroed array that only this writes).
+//   cpu_leapfrog44:  u^{n+1} = leapfrog_t4(u^n, u^{n−1}, v, s(v), lam12) in place over u^{n−1}; v over the WHOLE interior
+//                    must be cpu_lap4's of `cur`. The error check is cpu_leapfrog's.
+//   cpu_first_step_t4: u⁰ = φ everywhere (as cpu_first_step_field stores it), u¹ on the interior by first_step_t4 /
+//                    first_step_t4_psi; ψ's operator takes ψ from the source layout; v is scratch (left = lam·s(φ)).
+// A distance-2 neighbour outside the domain is −centre in both applications; no ghost layer is read.
+void cpu_lap4(const Layout& l, const Coeffs& c, const double* u, double* v, const LBox& box);
+void cpu_leapfrog44(const Layout& l, const Coeffs& c, const double* cur, const double* v, double* old_out, const LBox& box,
+                    const double* s, double ct, ErrAcc* acc);
+void cpu_first_step_t4(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
+                       const double* psi, double* v, double* u0, double* u1);
+
 // Sponge layers and the fused passes. An undamped pass of `steps` steps from damped levels u^{n−1}, u^n differs from
 // the damped one only within reach of the layers: u^{n+steps} on the slabs d < W + steps − 1 from each damped face (d:
 // nodes from the face), u^{n+steps−1} on d < W + steps − 2. sponge_boxes returns disjoint local boxes whose union is
@@ -289,6 +304,8 @@ class CpuSolver {
   // Problem::order = 4: every step uses the fourth-order operator, the start (eigenmode or set_initial) goes through
   // cpu_first_step_field; a box, receivers and sources work as before. Refused with messages starting "order:": a sponge
   // (Problem::validate), set_speed, energy / energy_sums, set_state.
+  // Problem::time_order = 4 (with order = 4): every step is cpu_lap4 + cpu_leapfrog44, the start cpu_first_step_t4;
+  // receivers work as before. Refused with "time_order:": set_sources (the forcing's τ⁴ terms are a follow-up).
   // With Problem::sponge set every step is the damped one (stencil.hpp leapfrog_damped); the start levels, set_initial,
   // set_state, receivers, sources (added after the damped step, as after the plain one) and energy work as before. The
   // error columns then have no meaning, and the energy decays.
@@ -336,6 +353,7 @@ class CpuSolver {
   int check_every_;
   Layout lay_;
   std::vector<double> u_[2];
+  std::vector<double> v_;                // time order 4: τ²L_h u^n (zeros outside the interior); empty otherwise
   std::vector<double> s_;
   SpongeTables sponge_;                  // Problem::sponge's coefficient tables (empty: no sponge)
   int final_ = 1;

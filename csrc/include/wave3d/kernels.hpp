@@ -113,6 +113,26 @@ void launch_leapfrog4(const Layout& l, const Coeffs& c, const double* cur, doubl
                       const double* d_s, double ct, Partial* partials, const LeapfrogTiling& t, hipStream_t stream,
                       int min_chunk = 16);
 
+// Fourth order in time (kernels_stencil44.hip; Problem::time_order = 4, Coeffs of such a problem): a step is two launches
+// with launch_leapfrog4's contract (boxes, tiling, min_chunk, one rank's layout that spans the domain).
+//   launch_lap4:       k_lap4, v = lam·s(u) on the interior nodes of the boxes and nothing else — bit-identical to cpu_lap4.
+//                      v's six faces must hold exact zeros (a buffer zeroed once that only this writes).
+//   launch_leapfrog44: k_leapfrog44, u^{n+1} = leapfrog_t4(u^n, u^{n−1}, v, s(v), lam12) in place over u^{n−1}, with v =
+//                      launch_lap4's of `cur` over the whole interior; partials as launch_leapfrog4 (leapfrog44_blocks of
+//                      them). Bit-identical to cpu_leapfrog44.
+//   launch_first_step_t4: u⁰ = φ, v = lam·s(φ), u¹ by first_step_t4 / first_step_t4_psi (k_first_step_field for u⁰, k_lap4,
+//                      k_first_step_t4) — bit-identical to cpu_first_step_t4; φ, ψ as launch_first_step_field takes them.
+// The ghost layer, the row padding and the planes outside the grid of u, u^{n−1} and v are never used as data.
+int leapfrog44_blocks(const Layout& l, const LBox* boxes, int nbox, const LeapfrogTiling& t, int min_chunk = 16);
+void launch_lap4(const Layout& l, const Coeffs& c, const double* u, double* v, const LBox* boxes, int nbox,
+                 const LeapfrogTiling& t, hipStream_t stream, int min_chunk = 16);
+void launch_leapfrog44(const Layout& l, const Coeffs& c, const double* cur, const double* v, double* old_out,
+                       const LBox* boxes, int nbox, const double* d_s, double ct, Partial* partials,
+                       const LeapfrogTiling& t, hipStream_t stream, int min_chunk = 16);
+void launch_first_step_t4(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
+                          const double* psi, double* v, double* u0, double* u1, const LeapfrogTiling& t,
+                          hipStream_t stream);
+
 // Sponge layers on the fused schedule (kernels_sponge.hip). An LDS pass of `steps` steps runs undamped; its two stored
 // outputs differ from the damped levels only on the slabs cpu.hpp sponge_boxes returns, which this recomputes from the
 // pass's INPUTS prev = u^{n−1}, cur = u^n with the damped operator: it writes out2 = u^{n+steps} and out1 =

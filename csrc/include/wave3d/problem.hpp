@@ -38,6 +38,7 @@ struct Problem {
   double Lz = 0.0;
   Sponge sponge;      // absorbing layers (off by default)
   int order = 2;      // spatial order of the Laplacian: 2 (7-point) or 4 (13-point, stencil.hpp d4sum_t)
+  int time_order = 2; // order of the time integrator: 2 (leapfrog) or 4 (stencil.hpp leapfrog_t4; needs order = 4)
 
   double Lx() const { return L; }
   double edge_y() const { return Ly > 0.0 ? Ly : L; }
@@ -67,7 +68,14 @@ struct Problem {
   // Order-aware guard. The largest symbol of −h²D₄ is 16/3 against 4 for the second-order difference, so the fourth-
   // order leapfrog is stable iff τ·sqrt(Σ 1/h_d²) ≤ sqrt(3)/2: the effective Courant number is courant()·2/sqrt(3).
   // order = 2: courant() itself, the same bits.
-  double courant_eff() const { return order == 4 ? courant() * (2.0 / std::sqrt(3.0)) : courant(); }
+  // time_order = 4: the step's symbol 2 − z + z²/12 stays in [−2, 2] iff 0 ≤ z ≤ 12 with z ≤ (16/3)·courant()², so the
+  // limit is courant() ≤ 3/2 and the effective number courant()·(2/3). time_order = 2 keeps its expressions and bits.
+  double courant_eff() const {
+    if (time_order == 4) return courant() * (2.0 / 3.0);
+    return order == 4 ? courant() * (2.0 / std::sqrt(3.0)) : courant();
+  }
+  // courant() at the stability limit of the scheme: 1 (order 2), sqrt(3)/2 (order 4), 3/2 (order 4, time order 4)
+  double courant_limit() const { return time_order == 4 ? 1.5 : order == 4 ? std::sqrt(3.0) / 2.0 : 1.0; }
   bool cfl_ok_eff() const { return courant_eff() <= 1.0; }
   // Largest stable τ for this grid (second-order operator; order 4: sqrt(3)/2 of it).
   double tau_max() const { return is_box() ? 1.0 / std::sqrt(inv_h2_sum()) : h() / std::sqrt(3.0); }
@@ -83,6 +91,8 @@ struct Problem {
     W3D_REQUIRE(order == 2 || order == 4, "order: the spatial order must be 2 or 4");
     W3D_REQUIRE(order == 2 || !sponge.on(), "order: no sponge layers with order = 4 (the damped form of the fourth-order "
                                             "operator is a follow-up)");
+    W3D_REQUIRE(time_order == 2 || time_order == 4, "time_order: the time order must be 2 or 4");
+    W3D_REQUIRE(time_order == 2 || order == 4, "time_order: 4 needs order = 4");
     W3D_REQUIRE(sponge.width >= 0, "sponge: the width must be >= 0");
     W3D_REQUIRE(!sponge.on() || 2 * static_cast<i64>(sponge.width) <= N - 1,
                 "sponge: two layers of width " + std::to_string(sponge.width) + " do not fit into the " +
@@ -105,6 +115,8 @@ struct Coeffs {
   double ry = 1.0, rz = 1.0;
   bool box = false;
   int order = 2;            // Problem::order
+  int time_order = 2;       // Problem::time_order
+  double lam12 = 0.0, lam24 = 0.0, lam6 = 0.0;  // time order 4 (stencil.hpp leapfrog_t4, first_step_t4): lam/12, /24, /6
 
   // force_box (tests): the box form also for a cube — with ry = rz = 1 it must reproduce the cube form's bits
   static Coeffs from(const Problem& p, bool force_box = false) {
@@ -129,6 +141,12 @@ struct Coeffs {
     if (p.order == 4) {  // (the 1/12 of the fourth-order difference; order 2 never comes here: no bit of it changes)
       c.lam = c.lam / 12.0;
       c.half_lam = c.half_lam / 12.0;
+    }
+    c.time_order = p.time_order;
+    if (p.time_order == 4) {
+      c.lam12 = c.lam / 12.0;
+      c.lam24 = c.lam / 24.0;
+      c.lam6 = c.lam / 6.0;
     }
     return c;
   }

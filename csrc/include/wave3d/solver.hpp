@@ -173,6 +173,12 @@ class GpuSolver {
   // "order:"): a world larger than 1 of any kind and group ranks (the halo would be two deep per step), fake ranks, the
   // push and copy-engine transports, a sponge (Problem::validate), set_speed, energy / energy_sums, set_state.
   bool order4() const { return sch_.prob.order == 4; }
+  // Problem::time_order = 4 (with order = 4): fourth order in time (stencil.hpp leapfrog_t4; CpuSolver is the definition,
+  // matched bit for bit). Every unit is a single step of two launches, k_lap4 (v = τ²L_h u^n into field buffer 2, which
+  // an order-4 solve otherwise leaves unused; allocated here where the schedule has two buffers) and k_leapfrog44; the
+  // start is launch_first_step_t4. Receivers, the check cadence, graph capture and set_initial work as for order 4;
+  // everything order 4 refuses stays refused, and set_sources is refused with a "time_order:" message.
+  bool time_order4() const { return sch_.prob.time_order == 4; }
   // Variable wave speed u_tt = c²(x)·Δu (cpu.hpp speed_to_local; CpuSolver is the definition, the fields match it bit for
   // bit). c: a global (N+1)³ field, face values ignored, interior values finite and > 0; courant()·max c ≤ 1 unless
   // `force`; nullptr clears it. lamf = lam·c² is a fifth device buffer in the solve layout, refused when it does not fit
@@ -331,6 +337,7 @@ class GpuSolver {
   bool own_s0_ = true;  // false: a GpuGroup "push" rank on the group's shared compute stream
   hipEvent_t ev_shell_ = nullptr, ev_halo_ = nullptr, ev_packed_ = nullptr;
   int n_full_ = 0, n_shell_ = 0, n_int_ = 0, n_fused_ = 0;  // error partials of each launch kind
+  bool own_v_ = false;                                      // time_order4(): buffer 2 was allocated for v alone
   int n_full4_ = 0;                                         // ... of the fourth-order single step (order4())
   int n_tb_ = 0;                                            // ... per level of a k_leapfrog_tb pass
   // deep-tb: per level, the partials of this unit's launches (shell lo, shell hi, interior) follow each other

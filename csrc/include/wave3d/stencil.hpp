@@ -132,6 +132,40 @@ W3D_HD double first_step_psi(double u1, double psi, double tau) {
 #endif
 }
 
+// Fourth order in time (Problem::time_order = 4; modified equation / Lax–Wendroff):
+//   u^{n+1} = 2u^n − u^{n−1} + τ²L_h u^n + (τ⁴/12)·L_h²u^n,
+// L_h the fourth-order operator, applied twice through d4sum_t with lam = τ²/(12h_x²) (Coeffs::lam):
+//   v = lap_t4(s(u^n), lam) = τ²L_h u^n on every interior node; v is exactly 0 on the six faces and, like u, its own odd
+//   reflection beyond a wall (L_h u is odd about a wall where u is), so s(v) takes −v for a distance-2 neighbour outside;
+//   u^{n+1} = leapfrog_t4(u^n, u^{n−1}, v, s(v), lam12), lam12 = lam/12: (τ⁴/12)L_h²u = lam12·s(v).
+// For the eigenmode s(φ) = −σφ and z = lam·σ: the step's symbol is 2 − z + z²/12 = 2cos(ω_hτ), stable iff 0 ≤ z ≤ 12.
+W3D_HD double lap_t4(double s, double lam) { return lam * s; }
+W3D_HD double leapfrog_t4(double c, double old, double v, double sv, double lam12) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fma(lam12, sv, __builtin_fma(2.0, c, -old) + v);
+#else
+  return std::fma(lam12, sv, (2.0 * c - old) + v);
+#endif
+}
+// Its first step, local error O(τ⁵): u¹ = φ + ½τ²L_hφ + (τ⁴/24)L_h²φ + τ(ψ + (τ²/6)L_hψ). With vφ = lap_t4(s(φ), lam):
+//   u¹ = first_step_t4(φ, vφ, s(vφ), lam24), lam24 = lam/24 — for the eigenmode the factor 1 − z/2 + z²/24 = cos(ω_hτ);
+//   with ψ: u¹ = first_step_t4_psi(u¹, ψ, s(ψ), lam6, τ), lam6 = lam/6, applied last and skipped entirely without ψ
+//   (first_step_psi's convention).
+W3D_HD double first_step_t4(double c, double v, double sv, double lam24) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fma(lam24, sv, __builtin_fma(0.5, v, c));
+#else
+  return std::fma(lam24, sv, std::fma(0.5, v, c));
+#endif
+}
+W3D_HD double first_step_t4_psi(double u1, double psi, double spsi, double lam6, double tau) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fma(tau, __builtin_fma(lam6, spsi, psi), u1);
+#else
+  return std::fma(tau, std::fma(lam6, spsi, psi), u1);
+#endif
+}
+
 // IEEE fused multiply-add on the host (bindings: the numpy emulators' rounding primitive)
 inline double fma_exact(double a, double b, double c) { return std::fma(a, b, c); }
 

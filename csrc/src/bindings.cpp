@@ -139,7 +139,8 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("faces", &Sponge::faces)
       .def_property_readonly("on", &Sponge::on);
   py::class_<Problem>(m, "Problem")
-      .def(py::init([](i64 N, double tau, int K, double L, double Ly, double Lz, const Sponge& sponge, int order) {
+      .def(py::init([](i64 N, double tau, int K, double L, double Ly, double Lz, const Sponge& sponge, int order,
+                       int time_order) {
              Problem p;
              p.N = N;
              p.tau = tau;
@@ -149,13 +150,17 @@ PYBIND11_MODULE(_C, m) {
              p.Lz = Lz;
              p.sponge = sponge;
              p.order = order;
+             p.time_order = time_order;
              p.validate();
              return p;
            }),
            py::arg("N") = 512, py::arg("tau") = 1e-3, py::arg("K") = 20, py::arg("L") = 1.0, py::kw_only(),
-           py::arg("Ly") = 0.0, py::arg("Lz") = 0.0, py::arg("sponge") = Sponge{}, py::arg("order") = 2)
+           py::arg("Ly") = 0.0, py::arg("Lz") = 0.0, py::arg("sponge") = Sponge{}, py::arg("order") = 2,
+           py::arg("time_order") = 2)
       .def_readwrite("sponge", &Problem::sponge)
       .def_readwrite("order", &Problem::order)
+      .def_readwrite("time_order", &Problem::time_order)
+      .def_property_readonly("courant_limit", &Problem::courant_limit)
       .def_property_readonly("courant_eff", &Problem::courant_eff)
       .def_property_readonly("cfl_ok_eff", &Problem::cfl_ok_eff)
       .def("validate", &Problem::validate)
@@ -195,7 +200,11 @@ PYBIND11_MODULE(_C, m) {
       .def_readonly("ry", &Coeffs::ry)
       .def_readonly("rz", &Coeffs::rz)
       .def_readonly("box", &Coeffs::box)
-      .def_readonly("order", &Coeffs::order);
+      .def_readonly("order", &Coeffs::order)
+      .def_readonly("time_order", &Coeffs::time_order)
+      .def_readonly("lam12", &Coeffs::lam12)
+      .def_readonly("lam24", &Coeffs::lam24)
+      .def_readonly("lam6", &Coeffs::lam6);
 
   m.def("sin_table_ext", [](const Problem& p) {
     auto v = sin_table_ext(p);
@@ -492,6 +501,51 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("old"), py::arg("box"), py::arg("s"),
       py::arg("ct") = 0.0, py::arg("check") = false, py::arg("sponge") = py::none(), py::arg("lamf") = py::none());
+  m.def("cpu_lap4",
+        [](const Layout& l, const Coeffs& c, const darr& u, darr v, const LBox& box) {
+          const double* up = ro_ptr(u, l.total, "u");
+          double* vp = mut_ptr(v, l.total, "v");
+          py::gil_scoped_release nogil;
+          cpu_lap4(l, c, up, vp, box);
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("u"), py::arg("v"), py::arg("box"),
+        "time order 4: v = lam s(u) on the nodes of `box`, nothing else of v is written");
+  m.def("cpu_leapfrog44",
+        [](const Layout& l, const Coeffs& c, const darr& cur, const darr& v, darr old, const LBox& box, const darr& s,
+           double ct, bool check) -> py::object {
+          const double* cp = ro_ptr(cur, l.total, "cur");
+          const double* vp = ro_ptr(v, l.total, "v");
+          double* op = mut_ptr(old, l.total, "old");
+          const double* sp = ro_ptr(s, l.N + 3, "s") + 1;
+          ErrAcc acc;
+          {
+            py::gil_scoped_release nogil;
+            cpu_leapfrog44(l, c, cp, vp, op, box, sp, ct, check ? &acc : nullptr);
+          }
+          if (!check) return py::none();
+          return py::make_tuple(acc.max, acc.sum);
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("v"), py::arg("old"), py::arg("box"), py::arg("s"),
+        py::arg("ct") = 0.0, py::arg("check") = false,
+        "time order 4: u^{n+1} = leapfrog_t4(u^n, u^{n-1}, v, s(v), lam12) in place over `old`");
+  m.def("cpu_first_step_t4",
+        [](const Layout& l, const Layout& src, const Coeffs& c, double tau, const darr& phi, py::object psi, darr v,
+           darr u0, darr u1) {
+          const double* fp = ro_ptr(phi, src.total, "phi");
+          const double* sp = nullptr;
+          darr psi_a;
+          if (!psi.is_none()) {
+            psi_a = psi.cast<darr>();
+            sp = ro_ptr(psi_a, src.total, "psi");
+          }
+          double* vp = mut_ptr(v, l.total, "v");
+          double* a = mut_ptr(u0, l.total, "u0");
+          double* b = mut_ptr(u1, l.total, "u1");
+          py::gil_scoped_release nogil;
+          cpu_first_step_t4(l, src, c, tau, fp, sp, vp, a, b);
+        },
+        py::arg("layout"), py::arg("src"), py::arg("coeffs"), py::arg("tau"), py::arg("phi"), py::arg("psi"), py::arg("v"),
+        py::arg("u0"), py::arg("u1"));
   m.def("cpu_error", [](const Layout& l, const darr& u, const LBox& box, const darr& s, double ct) {
     ErrAcc acc;
     cpu_error(l, ro_ptr(u, l.total, "u"), box, ro_ptr(s, l.N + 3, "s") + 1, ct, &acc);
@@ -727,6 +781,39 @@ PYBIND11_MODULE(_C, m) {
         py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("old"), py::arg("boxes"), py::arg("s"),
         py::arg("ct"), py::arg("partials"), py::arg("tiling"), py::arg("stream"), py::arg("min_chunk") = 16,
         "k_leapfrog4: the fourth-order single step (coeffs of an order = 4 problem)");
+  m.def("gpu_leapfrog44_blocks",
+        [](const Layout& l, const std::vector<LBox>& boxes, const LeapfrogTiling& t, int min_chunk) {
+          return leapfrog44_blocks(l, boxes.data(), static_cast<int>(boxes.size()), t, min_chunk);
+        },
+        py::arg("layout"), py::arg("boxes"), py::arg("tiling"), py::arg("min_chunk") = 16);
+  m.def("gpu_lap4",
+        [](const Layout& l, const Coeffs& c, std::uintptr_t u, std::uintptr_t v, const std::vector<LBox>& boxes,
+           const LeapfrogTiling& t, std::uintptr_t stream, int min_chunk) {
+          launch_lap4(l, c, dptr<const double>(u), dptr<double>(v), boxes.data(), static_cast<int>(boxes.size()), t,
+                      sptr(stream), min_chunk);
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("u"), py::arg("v"), py::arg("boxes"), py::arg("tiling"),
+        py::arg("stream"), py::arg("min_chunk") = 16, "k_lap4: v = lam s(u) (coeffs of a time_order = 4 problem)");
+  m.def("gpu_leapfrog44",
+        [](const Layout& l, const Coeffs& c, std::uintptr_t cur, std::uintptr_t v, std::uintptr_t old,
+           const std::vector<LBox>& boxes, std::uintptr_t s, double ct, std::uintptr_t partials, const LeapfrogTiling& t,
+           std::uintptr_t stream, int min_chunk) {
+          launch_leapfrog44(l, c, dptr<const double>(cur), dptr<const double>(v), dptr<double>(old), boxes.data(),
+                            static_cast<int>(boxes.size()), dptr<const double>(s) + 1, ct, dptr<Partial>(partials), t,
+                            sptr(stream), min_chunk);
+        },
+        py::arg("layout"), py::arg("coeffs"), py::arg("cur"), py::arg("v"), py::arg("old"), py::arg("boxes"), py::arg("s"),
+        py::arg("ct"), py::arg("partials"), py::arg("tiling"), py::arg("stream"), py::arg("min_chunk") = 16,
+        "k_leapfrog44: the update of a time_order = 4 step from v = gpu_lap4's of `cur`");
+  m.def("gpu_first_step_t4",
+        [](const Layout& l, const Layout& src, const Coeffs& c, double tau, std::uintptr_t phi, std::uintptr_t psi,
+           std::uintptr_t v, std::uintptr_t u0, std::uintptr_t u1, const LeapfrogTiling& t, std::uintptr_t stream) {
+          launch_first_step_t4(l, src, c, tau, dptr<const double>(phi), dptr<const double>(psi), dptr<double>(v),
+                               dptr<double>(u0), dptr<double>(u1), t, sptr(stream));
+        },
+        py::arg("layout"), py::arg("src"), py::arg("coeffs"), py::arg("tau"), py::arg("phi"), py::arg("psi"), py::arg("v"),
+        py::arg("u0"), py::arg("u1"), py::arg("tiling"), py::arg("stream"),
+        "the first step of a time_order = 4 solve (psi = 0: no psi term)");
   m.def("gpu_leapfrog_speed_supported", &leapfrog_speed_supported, py::arg("tiling"), py::arg("sponge"));
   m.def("gpu_sponge_box",
         [](const Layout& l, const Coeffs& c, std::uintptr_t tables, std::uintptr_t prev, std::uintptr_t cur,

@@ -157,6 +157,8 @@ void ShmGroup::barrier(double timeout_s) {
 CpuRankSolver::CpuRankSolver(const Problem& p, ShmGroup& g, int rank, int check_every, int threads)
     : prob_(p), g_(g), rank_(rank), check_every_(check_every) {
   prob_.validate();
+  W3D_REQUIRE(prob_.time_order == 2, "time_order: the distributed CPU program has single-operator steps only; time_order = 4 "
+                                     "runs in one CPU process (--cpu)");
   W3D_REQUIRE(prob_.order == 2, "order: the distributed CPU program exchanges one ghost layer per step; order = 4 runs in "
                                 "one CPU process (--cpu)");
   W3D_REQUIRE(!prob_.sponge.on(), "sponge: the distributed CPU program has no damped step (one CPU process: --cpu)");

@@ -273,6 +273,7 @@ void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* o
   if (box.empty()) return;
   if (c.order == 4) {
     W3D_REQUIRE(!sponge && !lamf, "order: no sponge and no speed field with order = 4");
+    W3D_REQUIRE(c.time_order == 2, "time_order: a time_order = 4 step is cpu_lap4 + cpu_leapfrog44");
     W3D_REQUIRE(l.nx == l.N + 1 && l.ny == l.N + 1 && l.nz == l.N + 1, "order: order = 4 needs a layout that spans the domain");
     if (c.box) {
       if (acc)
@@ -318,6 +319,147 @@ void cpu_leapfrog(const Layout& l, const Coeffs& c, const double* cur, double* o
   } else {
     leapfrog_impl<false, false>(l, c, cur, old_out, box, s, ct, nullptr);
   }
+}
+
+namespace {
+
+// Time order 4. s4_row: d4sum_t at node iz of the row f (any field in a layout with plane P and pitch R), a distance-2
+// neighbour outside the domain replaced by −centre.
+template <bool BOX>
+inline double s4_row(const double* f, i64 iz, i64 P, i64 R, bool xlo, bool xhi, bool ylo, bool yhi, bool zlo, bool zhi,
+                     const Coeffs& c) {
+  const double u = f[iz];
+  return d4sum_t<BOX>(u, xlo ? -u : f[iz - 2 * P], f[iz - P], f[iz + P], xhi ? -u : f[iz + 2 * P],
+                      ylo ? -u : f[iz - 2 * R], f[iz - R], f[iz + R], yhi ? -u : f[iz + 2 * R],
+                      zlo ? -u : f[iz - 2], f[iz - 1], f[iz + 1], zhi ? -u : f[iz + 2], c.ry, c.rz);
+}
+
+template <bool BOX>
+void lap4_impl(const Layout& l, const Coeffs& c, const double* u, double* v, const LBox& b) {
+  const i64 P = l.plane, R = l.pitch, N = l.N;
+#pragma omp parallel for schedule(static)
+  for (i64 ix = b.x0; ix < b.x1; ++ix) {
+    const bool xlo = l.gx0 + ix == 1, xhi = l.gx0 + ix == N - 1;
+    for (i64 iy = b.y0; iy < b.y1; ++iy) {
+      const bool ylo = l.gy0 + iy == 1, yhi = l.gy0 + iy == N - 1;
+      const i64 row = l.off(ix, iy, 0);
+      for (i64 iz = b.z0; iz < b.z1; ++iz)
+        v[row + iz] = lap_t4(s4_row<BOX>(u + row, iz, P, R, xlo, xhi, ylo, yhi, l.gz0 + iz == 1, l.gz0 + iz == N - 1, c),
+                             c.lam);
+    }
+  }
+}
+
+template <bool CHECK, bool BOX>
+void leapfrog44_impl(const Layout& l, const Coeffs& c, const double* cur, const double* v, double* out, const LBox& b,
+                     const double* s, double ct, ErrAcc* acc) {
+  const i64 nxp = b.x1 - b.x0;
+  std::vector<ErrAcc> part(CHECK ? static_cast<size_t>(nxp) : 0);
+  const i64 P = l.plane, R = l.pitch, N = l.N;
+#pragma omp parallel for schedule(static)
+  for (i64 ix = b.x0; ix < b.x1; ++ix) {
+    double emax = 0.0, esum = 0.0;
+    const double sx = s[l.gx0 + ix];
+    const bool xlo = l.gx0 + ix == 1, xhi = l.gx0 + ix == N - 1;
+    for (i64 iy = b.y0; iy < b.y1; ++iy) {
+      const double sxy = analytic_row(sx, s[l.gy0 + iy], ct);
+      const bool ylo = l.gy0 + iy == 1, yhi = l.gy0 + iy == N - 1;
+      const i64 row = l.off(ix, iy, 0);
+      const double* cr = cur + row;
+      const double* vr = v + row;
+      double* orow = out + row;
+      for (i64 iz = b.z0; iz < b.z1; ++iz) {
+        const double sv = s4_row<BOX>(vr, iz, P, R, xlo, xhi, ylo, yhi, l.gz0 + iz == 1, l.gz0 + iz == N - 1, c);
+        const double w = leapfrog_t4(cr[iz], orow[iz], vr[iz], sv, c.lam12);
+        orow[iz] = w;
+        if (CHECK) {
+          const double e = std::fabs(w - sxy * s[l.gz0 + iz]);
+          emax = e > emax ? e : emax;
+          esum = err_sq_acc(e, esum);
+        }
+      }
+    }
+    if (CHECK) part[static_cast<size_t>(ix - b.x0)] = ErrAcc{emax, esum};
+  }
+  if (CHECK) {
+    for (const auto& p : part) {
+      acc->max = p.max > acc->max ? p.max : acc->max;
+      acc->sum += p.sum;
+    }
+  }
+}
+
+template <bool BOX>
+void first_step_t4_impl(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* psi,
+                        const double* v, const double* u0, double* u1, const LBox& b) {
+  const i64 P = l.plane, R = l.pitch, N = l.N;
+#pragma omp parallel for schedule(static)
+  for (i64 ix = b.x0; ix < b.x1; ++ix) {
+    const bool xlo = l.gx0 + ix == 1, xhi = l.gx0 + ix == N - 1;
+    for (i64 iy = b.y0; iy < b.y1; ++iy) {
+      const bool ylo = l.gy0 + iy == 1, yhi = l.gy0 + iy == N - 1;
+      const i64 row = l.off(ix, iy, 0);
+      const double* prow = psi ? psi + src.off(ix, iy, 0) : nullptr;
+      for (i64 iz = b.z0; iz < b.z1; ++iz) {
+        const bool zlo = l.gz0 + iz == 1, zhi = l.gz0 + iz == N - 1;
+        const double sv = s4_row<BOX>(v + row, iz, P, R, xlo, xhi, ylo, yhi, zlo, zhi, c);
+        double w = first_step_t4(u0[row + iz], v[row + iz], sv, c.lam24);
+        if (prow)
+          w = first_step_t4_psi(w, prow[iz], s4_row<BOX>(prow, iz, src.plane, src.pitch, xlo, xhi, ylo, yhi, zlo, zhi, c),
+                                c.lam6, tau);
+        u1[row + iz] = w;
+      }
+    }
+  }
+}
+
+void require_t4(const Layout& l, const Coeffs& c, const LBox& box) {
+  W3D_REQUIRE(c.time_order == 4 && c.order == 4, "time_order: the coefficients of a time_order = 4 problem are needed");
+  W3D_REQUIRE(l.nx == l.N + 1 && l.ny == l.N + 1 && l.nz == l.N + 1 && l.gx0 == 0 && l.gy0 == 0 && l.gz0 == 0,
+              "time_order: time_order = 4 needs a layout that spans the domain");
+  W3D_REQUIRE(box.x0 >= 1 && box.x1 <= l.N && box.y0 >= 1 && box.y1 <= l.N && box.z0 >= 1 && box.z1 <= l.N,
+              "time_order: the box must lie inside the global interior");
+}
+
+}  // namespace
+
+void cpu_lap4(const Layout& l, const Coeffs& c, const double* u, double* v, const LBox& box) {
+  if (box.empty()) return;
+  require_t4(l, c, box);
+  if (c.box)
+    lap4_impl<true>(l, c, u, v, box);
+  else
+    lap4_impl<false>(l, c, u, v, box);
+}
+
+void cpu_leapfrog44(const Layout& l, const Coeffs& c, const double* cur, const double* v, double* old_out, const LBox& box,
+                    const double* s, double ct, ErrAcc* acc) {
+  if (box.empty()) return;
+  require_t4(l, c, box);
+  if (c.box) {
+    if (acc)
+      leapfrog44_impl<true, true>(l, c, cur, v, old_out, box, s, ct, acc);
+    else
+      leapfrog44_impl<false, true>(l, c, cur, v, old_out, box, s, ct, nullptr);
+  } else if (acc) {
+    leapfrog44_impl<true, false>(l, c, cur, v, old_out, box, s, ct, acc);
+  } else {
+    leapfrog44_impl<false, false>(l, c, cur, v, old_out, box, s, ct, nullptr);
+  }
+}
+
+void cpu_first_step_t4(const Layout& l, const Layout& src, const Coeffs& c, double tau, const double* phi,
+                       const double* psi, double* v, double* u0, double* u1) {
+  const LBox box = compute_box(l);
+  require_t4(l, c, box);
+  // u⁰ = φ over the whole allocation and zeros in u¹ outside the interior, exactly as the (4, 2) start stores them (its
+  // u¹ on the interior is replaced below)
+  cpu_first_step_field(l, src, c, tau, phi, nullptr, u0, u1, nullptr);
+  cpu_lap4(l, c, u0, v, box);
+  if (c.box)
+    first_step_t4_impl<true>(l, src, c, tau, psi, v, u0, u1, box);
+  else
+    first_step_t4_impl<false>(l, src, c, tau, psi, v, u0, u1, box);
 }
 
 namespace {

@@ -23,6 +23,7 @@ CpuSolver::CpuSolver(const Problem& p, int check_every, int threads) : prob_(p),
   lay_ = make_layout(prob_, b);
   u_[0].assign(static_cast<size_t>(lay_.total), 0.0);
   u_[1].assign(static_cast<size_t>(lay_.total), 0.0);
+  if (prob_.time_order == 4) v_.assign(static_cast<size_t>(lay_.total), 0.0);  // (only cpu_lap4 writes it: the faces stay 0)
   s_ = sin_table_ext(prob_);
   if (prob_.sponge.on()) sponge_ = sponge_tables(prob_);
 }
@@ -213,6 +214,8 @@ std::vector<double> source_addends(const Problem& p, const i64* ijk, int Q, cons
 }
 
 void CpuSolver::set_sources(const i64* ijk, int Q, const double* w) {
+  W3D_REQUIRE(Q == 0 || prob_.time_order == 2, "time_order: no point sources with time_order = 4 (the forcing's tau^4 terms "
+                                               "are a follow-up)");
   W3D_REQUIRE(Q == 0 || resume_n_ == 0, "sources: not together with set_state (a resumed solve has no step 0 to start "
                                         "the wavelet from)");
   std::vector<double> a = source_addends(prob_, ijk, Q, w);
@@ -252,6 +255,16 @@ CpuResult CpuSolver::run() {
   if (resume_n_ > 0) {
     u_[0] = resume_[0];
     u_[1] = resume_[1];
+  } else if (prob_.time_order == 4) {
+    // time order 4: φ (set_initial's, or the eigenmode array) and ψ through cpu_first_step_t4
+    std::vector<double> phi0;
+    Layout il = init_lay_;
+    if (!initial_) {
+      il = initial_layout(prob_, lay_);
+      phi0 = eigenmode_local(prob_, il);
+    }
+    cpu_first_step_t4(lay_, il, c, prob_.tau, initial_ ? init_[0].data() : phi0.data(),
+                      initial_ && !init_[1].empty() ? init_[1].data() : nullptr, v_.data(), u_[0].data(), u_[1].data());
   } else if (initial_) {
     cpu_first_step_field(lay_, init_lay_, c, prob_.tau, init_[0].data(), init_[1].empty() ? nullptr : init_[1].data(),
                          u_[0].data(), u_[1].data(), lamf);
@@ -296,7 +309,14 @@ CpuResult CpuSolver::run() {
   int cur = 1, old = 0;
   for (int n = n_start; n <= prob_.K - 1; ++n) {
     const double tc = now_s();
-    if (is_check[static_cast<size_t>(n + 1)]) {
+    if (prob_.time_order == 4) {
+      const bool chk = is_check[static_cast<size_t>(n + 1)] != 0;
+      ErrAcc a;
+      cpu_lap4(lay_, c, u_[cur].data(), v_.data(), box);
+      cpu_leapfrog44(lay_, c, u_[cur].data(), v_.data(), u_[old].data(), box, s, chk ? time_factor(prob_, n + 1) : 0.0,
+                     chk ? &a : nullptr);
+      if (chk) record(n + 1, a);
+    } else if (is_check[static_cast<size_t>(n + 1)]) {
       ErrAcc a;
       cpu_leapfrog(lay_, c, u_[cur].data(), u_[old].data(), box, s, time_factor(prob_, n + 1), &a, sp, lamf);
       record(n + 1, a);

@@ -35,6 +35,7 @@ void write_dump(const std::string& prefix, const Problem& p, const Layout& l, co
   if (speed) j << ", \"speed\": [" << speed->cmin << ", " << speed->cmax << "]";
   // (the spatial order, when it is not 2 — "order" is the array's memory order here; absent for order 2)
   if (p.order != 2) j << ", \"space_order\": " << p.order;
+  if (p.time_order != 2) j << ", \"time_order\": " << p.time_order;
   j << ", \"tau\": " << p.tau << ", \"step\": " << step << ", \"t\": " << step * p.tau
     << ", \"shape\": [" << l.nx << ", " << l.ny << ", " << l.nz << "], \"offset\": [" << l.gx0 << ", " << l.gy0
     << ", " << l.gz0 << "], \"global_shape\": [" << p.N + 1 << ", " << p.N + 1 << ", " << p.N + 1
@@ -163,6 +164,7 @@ void write_traces(const std::string& out, const Problem& p, const std::vector<i6
     << ", \"L\": " << p.L;
   if (p.is_box()) j << ", \"box\": [" << p.L << ", " << p.edge_y() << ", " << p.edge_z() << "]";
   if (p.order != 2) j << ", \"space_order\": " << p.order;
+  if (p.time_order != 2) j << ", \"time_order\": " << p.time_order;
   j << ", \"tau\": " << p.tau << ", \"shape\": [" << rows << ", " << R << "], \"nodes\": [";
   for (size_t r = 0; r < R; ++r)
     j << (r ? ", [" : "[") << ijk[3 * r] << ", " << ijk[3 * r + 1] << ", " << ijk[3 * r + 2] << "]";

@@ -102,6 +102,11 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
     W3D_HIP(hipMalloc(&u_[b], static_cast<size_t>(sch_.lay.bytes())));
     W3D_HIP(hipMemset(u_[b], 0, static_cast<size_t>(sch_.lay.bytes())));
   }
+  if (time_order4() && !u_[2]) {  // v = τ²L_h u^n: buffer 2, which a single-step schedule does not allocate itself
+    W3D_HIP(hipMalloc(&u_[2], static_cast<size_t>(sch_.lay.bytes())));
+    W3D_HIP(hipMemset(u_[2], 0, static_cast<size_t>(sch_.lay.bytes())));
+    own_v_ = true;
+  }
   if (sch_.push) push_alloc();
   const std::vector<double> s = sin_table_ext(sch_.prob);
   W3D_HIP(hipMalloc(&d_s_, s.size() * sizeof(double)));
@@ -155,6 +160,7 @@ GpuSolver::GpuSolver(const Problem& prob, const SolverOptions& opt, int rank, in
   n_dint_ = sch_.dint.empty() ? 0 : leapfrog2_partials(sch_.lay, sch_.dint, sch_.opt.tiling2);
   n_deep += n_dint_;
   if (order4()) n_full4_ = leapfrog4_blocks(sch_.lay, &sch_.full, 1, sch_.opt.tiling);
+  if (time_order4()) n_full4_ = leapfrog44_blocks(sch_.lay, &sch_.full, 1, sch_.opt.tiling);
   n_partials_ = std::max({n_full_, n_full4_, n_shell_ + n_int_, error_blocks(sch_.lay, sch_.full), n_fused_, n_deep,
                           sch_.opt.init2 ? init_two_partials(sch_.lay) : 0, 1});
   W3D_HIP(hipMalloc(&partials_, static_cast<size_t>(n_partials_) * sizeof(Partial)));
@@ -319,7 +325,7 @@ GpuSolver::~GpuSolver() {
 }
 
 size_t GpuSolver::device_bytes() const {
-  return static_cast<size_t>(sch_.nbuf + (speed() ? 1 : 0)) * static_cast<size_t>(sch_.lay.bytes()) +
+  return static_cast<size_t>(sch_.nbuf + (speed() ? 1 : 0) + (own_v_ ? 1 : 0)) * static_cast<size_t>(sch_.lay.bytes()) +
          recv_bytes_ + send_bytes_ + static_cast<size_t>(n_partials_) * sizeof(Partial) +
          static_cast<size_t>(sch_.prob.N + 3) * sizeof(double) * (sponge() ? 7u : 1u) + tb_bytes_ +
          ((init_[0] ? 1u : 0u) + (init_[1] ? 1u : 0u)) * static_cast<size_t>(init_lay_.bytes()) +
@@ -425,6 +431,8 @@ void GpuSolver::record_unit(const UnitPlan& u) {
 
 void GpuSolver::set_sources(const i64* ijk, int Q, const double* w) {
   if (Q > 0) {
+    W3D_REQUIRE(!time_order4(), "time_order: no point sources with time_order = 4 (the forcing's tau^4 terms are a "
+                                "follow-up)");
     W3D_REQUIRE(!sch_.push, "sources: not on the push transport (its ghost planes live in the staging buffers, which the "
                             "source kernel does not correct); use a loopback or rccl-self group");
     W3D_REQUIRE(!sch_.opt.fake_comm, "sources: a fake rank's ghosts are never delivered");
@@ -574,7 +582,11 @@ void GpuSolver::phase_init() {
     // (a speed field without set_initial: init_[0] is the eigenmode array, init_[1] null; the coefficient per node.
     // order 4 without set_initial likewise; its coefficients select the kernel's fourth-order form)
     timed(kPhaseInit, s0_, [&] {
-      launch_first_step_field(sch_.lay, init_lay_, coef_, sch_.prob.tau, init_[0], init_[1], u_[0], u_[1], s0_, lamf_dev_);
+      if (time_order4())  // (v: buffer 2, whose faces stay the zeros of its allocation — only k_lap4 writes it)
+        launch_first_step_t4(sch_.lay, init_lay_, coef_, sch_.prob.tau, init_[0], init_[1], u_[2], u_[0], u_[1],
+                             sch_.opt.tiling, s0_);
+      else
+        launch_first_step_field(sch_.lay, init_lay_, coef_, sch_.prob.tau, init_[0], init_[1], u_[0], u_[1], s0_, lamf_dev_);
     });
     timed(kPhaseCheck, s0_, [&] {
       if (energy_part_ && sch_.world == 1 && !speed() && !order4()) {  // E^{1/2}, kept in its device slot
@@ -837,7 +849,14 @@ void GpuSolver::unit_interior(int i) {
   const bool wait = needs_exchange(i) && xstream() != s0_ && (!loopback_ || sch_.sdma);
   int np = 0;  // partials to reduce
   bool joined = false;
-  if (order4()) {  // (single steps only: plan_units; one rank, so no shell preceded it)
+  if (time_order4()) {  // (two launches per single step: v = τ²L_h u^n into buffer 2, then the update from v)
+    timed(kPhaseCompute, s0_, [&] {
+      launch_lap4(sch_.lay, coef_, u_[cur_], u_[2], &sch_.full, 1, sch_.opt.tiling, s0_);
+      launch_leapfrog44(sch_.lay, coef_, u_[cur_], u_[2], u_[old_], &sch_.full, 1, s, ct, chk ? partials_ : nullptr,
+                        sch_.opt.tiling, s0_);
+    });
+    np = n_full4_;
+  } else if (order4()) {  // (single steps only: plan_units; one rank, so no shell preceded it)
     timed(kPhaseCompute, s0_, [&] {
       launch_leapfrog4(sch_.lay, coef_, u_[cur_], u_[old_], &sch_.full, 1, s, ct, chk ? partials_ : nullptr, sch_.opt.tiling, s0_);
     });

@@ -75,6 +75,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="spatial order of the Laplacian (default 2). 4: the 13-point stencil with the odd reflection at the "
                          "walls, stable for courant <= sqrt(3)/2; one native rank (hip or cpu); not with --sponge, --speed, "
                          "--resume or --energy")
+    ap.add_argument("--time-order", type=int, default=2, choices=(2, 4), dest="time_order",
+                    help="order of the time integrator (default 2). 4: u^{n+1} = 2u^n - u^{n-1} + tau^2 L u^n + tau^4/12 L^2 u^n, "
+                         "needs --order 4, stable for courant <= 3/2; runs where --order 4 runs; not with --sources")
     ap.add_argument("--force", action="store_true", help="run even if the CFL condition is violated")
     ap.add_argument("--quiet", action="store_true")
     return ap
@@ -104,6 +107,10 @@ def main(argv=None) -> int:
         ap.error("--sources and --resume exclude each other")
     if a.order == 4 and (a.resume or a.speed or a.sponge or a.energy):
         ap.error("order: --order 4 not together with --resume, --speed, --sponge or --energy")
+    if a.time_order == 4 and a.order != 4:
+        ap.error("time_order: 4 needs order = 4 (--order 4)")
+    if a.time_order == 4 and a.sources:
+        ap.error("time_order: --time-order 4 not together with --sources")
     if a.speed and a.resume:
         ap.error("speed: not together with --resume")
     if bool(a.receivers) != bool(a.traces):
@@ -132,12 +139,18 @@ def main(argv=None) -> int:
     from .utils.report import gcell_per_s
 
     spec = ProblemSpec(N=a.N, tau=a.tau, K=a.K, L=a.L, check_every=a.check_every,
-                       Ly=box[1] if box else None, Lz=box[2] if box else None, sponge=sponge, order=a.order)
+                       Ly=box[1] if box else None, Lz=box[2] if box else None, sponge=sponge, order=a.order,
+                       time_order=a.time_order)
     if spec.sponge is not None:
         print("wave3d: sponge layers are set: the error columns compare with the undamped eigenmode and have no meaning",
               file=sys.stderr)
     box_note = " box=" + ",".join(f"{e:g}" for e in spec.edges) if spec.is_box else ""
-    if spec.order == 4 and not spec.cfl_ok:
+    if spec.time_order == 4 and not spec.cfl_ok:
+        print(f"wave3d: CFL violated: courant = {spec.courant:.4f} > 3/2 for --order 4 --time-order 4 (effective "
+              f"{spec.courant_eff:.4f} > 1, tau_max = {spec.tau_max * 1.5:.3e})", file=sys.stderr)
+        if not a.force:
+            return 2
+    elif spec.order == 4 and not spec.cfl_ok:
         print(f"wave3d: CFL violated: courant = {spec.courant:.4f} > sqrt(3)/2 for --order 4 (effective "
               f"{spec.courant_eff:.4f} > 1, tau_max = {spec.tau_max * math.sqrt(3.0) / 2.0:.3e})", file=sys.stderr)
         if not a.force:
@@ -264,16 +277,20 @@ def main(argv=None) -> int:
                            **({"sponge": list(spec.sponge)} if spec.sponge is not None else {}),
                            **({"speed": speed_range} if speed_range is not None else {}),
                            **({"order": spec.order} if spec.order != 2 else {}),
+                           **({"time_order": spec.time_order} if spec.time_order != 2 else {}),
                            "steps": [[n, m, e] for n, m, e in zip(r.steps, r.max_err, r.rms_err)]}, f)
     if a.traces:
         dumpio.save_traces(a.traces, s.traces().numpy(), nodes, N=a.N, K=a.K, L=a.L, tau=a.tau, box=spec.edges,
-                           extra={"space_order": spec.order} if spec.order != 2 else None)
+                           extra={**({"space_order": spec.order} if spec.order != 2 else {}),
+                                  **({"time_order": spec.time_order} if spec.time_order != 2 else {})} or None)
     if a.dump or a.checkpoint:
         sponge_meta = {"sponge": list(spec.sponge)} if spec.sponge is not None else None  # (absent without a sponge)
         if speed_range is not None:  # (... and a speed field only when set: the interior minimum and maximum of c)
             sponge_meta = {**(sponge_meta or {}), "speed": speed_range}
         if spec.order != 2:  # (... and the spatial order only when it is not 2; "order" is the memory order there)
             sponge_meta = {**(sponge_meta or {}), "space_order": spec.order}
+        if spec.time_order != 2:
+            sponge_meta = {**(sponge_meta or {}), "time_order": spec.time_order}
 
         def write(prefix, which):
             if s.transport in ("loopback", "rccl-self", "push", "sdma"):

@@ -55,7 +55,11 @@ class ProblemSpec:
 
     ``order`` is the spatial order of the Laplacian: 2 (the 7-point stencil) or 4 (the 13-point one with the odd
     reflection u_{-1} = -u_1 at the Dirichlet walls; CLI ``--order 4``). Order 4 is stable for
-    tau sqrt(sum 1/h_d^2) <= sqrt(3)/2 (``courant_eff``) and runs on one native rank, without a sponge."""
+    tau sqrt(sum 1/h_d^2) <= sqrt(3)/2 (``courant_eff``) and runs on one native rank, without a sponge.
+
+    ``time_order`` is the order of the time integrator: 2 (leapfrog) or 4 (the modified-equation scheme u^{n+1} = 2u^n -
+    u^{n-1} + tau^2 L u^n + tau^4/12 L^2 u^n; CLI ``--time-order 4``). It needs ``order = 4``, is stable for
+    tau sqrt(sum 1/h_d^2) <= 3/2 and runs where order 4 runs, without point sources."""
 
     N: int = 512
     tau: float = 1e-3
@@ -67,10 +71,15 @@ class ProblemSpec:
     Lz: float | None = None
     sponge: tuple | int | None = None
     order: int = 2
+    time_order: int = 2
 
     def __post_init__(self) -> None:
         if self.order not in (2, 4):
             raise ValueError("order: the spatial order must be 2 or 4")
+        if self.time_order not in (2, 4):
+            raise ValueError("time_order: the time order must be 2 or 4")
+        if self.time_order == 4 and self.order != 4:
+            raise ValueError("time_order: 4 needs order = 4")
         if self.sponge is not None:
             sp = self.sponge if isinstance(self.sponge, (tuple, list)) else (self.sponge,)
             if not 1 <= len(sp) <= 3:
@@ -164,7 +173,14 @@ class ProblemSpec:
     def courant_eff(self) -> float:
         """The order-aware Courant number: courant·2/√3 for order 4 (the largest symbol of −h²D₄ is 16/3 against 4), courant
         itself for order 2 (problem.hpp::Problem::courant_eff)."""
+        if self.time_order == 4:  # (the step's symbol 2 - z + z^2/12 stays in [-2, 2] iff z = 16/3 courant^2 <= 12)
+            return self.courant * (2.0 / 3.0)
         return self.courant * (2.0 / math.sqrt(3.0)) if self.order == 4 else self.courant
+
+    @property
+    def courant_limit(self) -> float:
+        """``courant`` at the scheme's stability limit: 1, sqrt(3)/2 for order 4, 3/2 for order 4 with time order 4."""
+        return 1.5 if self.time_order == 4 else math.sqrt(3.0) / 2.0 if self.order == 4 else 1.0
 
     @property
     def cfl_ok(self) -> bool:
@@ -192,6 +208,8 @@ class ProblemSpec:
         kw = {} if self.sponge is None else {"sponge": C.Sponge(*self.sponge)}
         if self.order != 2:
             kw["order"] = self.order
+        if self.time_order != 2:
+            kw["time_order"] = self.time_order
         if self.Ly is None and self.Lz is None:
             return C.Problem(self.N, self.tau, self.K, self.L, **kw)
         _, ly, lz = self.edges
@@ -207,6 +225,8 @@ class ProblemSpec:
             d["Ly"], d["Lz"] = self.edges[1], self.edges[2]
         if self.order == 2:  # (... and so is a second-order spec's)
             d.pop("order")
+        if self.time_order == 2:
+            d.pop("time_order")
         if self.sponge is None:  # (... and so is a spec's without a sponge)
             d.pop("sponge")
         else:
@@ -234,7 +254,9 @@ def analytic(spec: ProblemSpec, n: int, dtype=torch.float64, device="cpu") -> to
 # closed-form oracle
 # ----------------------------------------------------------------------------------------------------------------
 def oracle_errors(spec: ProblemSpec, steps: list[int] | None = None, dps: int = 50) -> dict[int, tuple[float, float]]:
-    """Exact (L∞, RMS-interior) error of the discrete scheme at each step, from the closed form of SURVEY.md §1.6."""
+    """Exact (L∞, RMS-interior) error of the discrete scheme at each step, from the closed form of SURVEY.md §1.6.
+    ``order = 4``: λ_h = Σ_d (30 − 32cos(π/N) + 2cos(2π/N))/(12h_d²); ``time_order = 4``: cos θ = 1 − z/2 + z²/24 with
+    z = τ²λ_h, the first step's factor and half the recurrence's symbol 2 − z + z²/12."""
     import mpmath as mp
 
     mp.mp.dps = dps
@@ -250,7 +272,12 @@ def oracle_errors(spec: ProblemSpec, steps: list[int] | None = None, dps: int = 
     else:
         lam = 3 * (4 / h**2) * mp.sin(mp.pi * h / (2 * L)) ** 2
         a_t = mp.pi * mp.sqrt(3 / L**2)
-    cos_theta = 1 - tau**2 * lam / 2
+    if spec.order == 4:
+        th = mp.pi / N
+        lam = (30 - 32 * mp.cos(th) + 2 * mp.cos(2 * th)) / 12 * mp.fsum(1 / (mp.mpf(e) / N) ** 2 for e in spec.edges)
+        a_t = mp.pi * mp.sqrt(mp.fsum(1 / mp.mpf(e) ** 2 for e in spec.edges))
+    z = tau**2 * lam
+    cos_theta = 1 - z / 2 + z**2 / 24 if spec.time_order == 4 else 1 - z / 2
     theta = mp.acos(cos_theta)
     # max_i |sin(π i/N)|³ and Σ_interior φ² = (Σ_i sin²(π i/N))³
     s_max = max(abs(mp.sin(mp.pi * i / N)) for i in range(N + 1))

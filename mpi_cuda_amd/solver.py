@@ -110,6 +110,10 @@ class Solver:
             spec = dataclasses.replace(spec, sponge=sponge)
 
         if not spec.cfl_ok and not force:
+            if spec.time_order == 4:
+                raise ValueError(f"CFL violated: courant = {spec.courant:.4f} > 3/2 for order = 4, time_order = 4 "
+                                 f"(effective {spec.courant_eff:.4f} > 1, tau_max = {spec.tau_max * 1.5:.3e}); "
+                                 "pass force=True to run anyway")
             if spec.order == 4:
                 raise ValueError(f"CFL violated: courant = {spec.courant:.4f} > sqrt(3)/2 for order = 4 (effective "
                                  f"{spec.courant_eff:.4f} > 1, tau_max = {spec.tau_max * math.sqrt(3.0) / 2.0:.3e}); "
@@ -511,6 +515,8 @@ class Solver:
         several processes."""
         import numpy as np
 
+        if self.spec.time_order == 4 and len(nodes) > 0:
+            raise ValueError("time_order: no point sources with time_order = 4 (the forcing's tau^4 terms are a follow-up)")
         if self.runtime == "process":
             raise NotImplementedError("sources: runtime='process' is out of scope (the rank processes take no source "
                                       "list); run in process, or use bin/wave3d --sources")

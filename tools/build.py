@@ -47,6 +47,7 @@ CPU_FLAGS = COMMON + ["-fopenmp", "-march=x86-64-v3"]
 LIB_SOURCES = [
     ("src/kernels_stencil.hip", "hip"),
     ("src/kernels_stencil4.hip", "hip"),
+    ("src/kernels_stencil44.hip", "hip"),
     ("src/kernels_halo.hip", "hip"),
     ("src/kernels_leapfrog2.hip", "hip"),
     ("src/kernels_init2.hip", "hip"),

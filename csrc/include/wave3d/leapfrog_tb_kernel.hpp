@@ -9,6 +9,7 @@
 #include <string>
 #include <type_traits>
 
+#include "wave3d/device_util.hpp"
 #include "wave3d/kernels.hpp"
 #include "wave3d/pass_grid.hpp"
 #include "wave3d/stencil.hpp"
@@ -28,16 +29,6 @@ typedef __attribute__((address_space(1))) double gdouble;
 template <class P>
 __device__ __forceinline__ P tb_ptr_at(const P* slot) {
   return *static_cast<const volatile P*>(slot);
-}
-
-__device__ __forceinline__ void wave_reduce(double& m, double& s) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double om = __shfl_xor(m, o, 64);
-    const double os = __shfl_xor(s, o, 64);
-    m = om > m ? om : m;
-    s = s + os;
-  }
 }
 
 // A y/z neighbour read from an LDS plane: one ds_read_b64 each. Plain reads of one base were paired by the compiler

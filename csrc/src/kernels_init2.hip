@@ -14,6 +14,7 @@
 // untouched (they are zero from allocation on and are never written by any kernel).
 #include <hip/hip_runtime.h>
 
+#include "wave3d/device_util.hpp"
 #include "wave3d/kernels.hpp"
 #include "wave3d/stencil.hpp"
 
@@ -21,19 +22,8 @@ namespace wave3d {
 
 namespace {
 
-using v2d = double __attribute__((ext_vector_type(2)));
 constexpr int kWaves = 4;
 constexpr int kOutPairs = 62;
-
-__device__ __forceinline__ void wave_reduce(double& m, double& s) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double om = __shfl_xor(m, o, 64);
-    const double os = __shfl_xor(s, o, 64);
-    m = om > m ? om : m;
-    s = s + os;
-  }
-}
 
 struct Init2Params {
   double* u1;

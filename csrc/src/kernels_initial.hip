@@ -12,23 +12,13 @@
 // the other.
 #include <hip/hip_runtime.h>
 
+#include "wave3d/device_util.hpp"
 #include "wave3d/kernels.hpp"
 #include "wave3d/stencil.hpp"
 
 namespace wave3d {
 
-#define W3D_HIP_CHECK(expr)                                                                          \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess) ::wave3d::fail(std::string(#expr) + ": " + hipGetErrorString(_e));          \
-  } while (0)
-
 namespace {
-
-using v2d = double __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v2d ld2(const double* p) { return *reinterpret_cast<const v2d*>(p); }
-__device__ __forceinline__ void st2(double* p, v2d v) { *reinterpret_cast<v2d*>(p) = v; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // first step from stored fields
@@ -133,8 +123,8 @@ __global__ __launch_bounds__(256) void k_first_step_field(const FirstStepParams 
     }
   }
   const i64 o = static_cast<i64>(blockIdx.y) * p.plane + 2 * static_cast<i64>(q);
-  st2(p.u0 + o, w0);
-  st2(p.u1 + o, w1);
+  st2<false>(p.u0 + o, w0);
+  st2<false>(p.u1 + o, w1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 // pass reads buffers (prev, cur) and writes (out1, out2); the solver rotates four buffers.
 #include <hip/hip_runtime.h>
 
+#include "wave3d/device_util.hpp"
 #include "wave3d/kernels.hpp"
 #include "wave3d/stencil.hpp"
 
@@ -25,29 +26,8 @@ namespace wave3d {
 
 namespace {
 
-using v2d = double __attribute__((ext_vector_type(2)));
 constexpr int kWaves = 4;       // waves per workgroup (independent)
 constexpr int kOutPairs = 62;   // output pairs per wave (64 lanes minus a halo pair on each side)
-
-__device__ __forceinline__ v2d ld2(const double* p) { return *reinterpret_cast<const v2d*>(p); }
-
-template <bool NT>
-__device__ __forceinline__ void st2(double* p, v2d v) {
-  if (NT)
-    __builtin_nontemporal_store(v, reinterpret_cast<v2d*>(p));
-  else
-    *reinterpret_cast<v2d*>(p) = v;
-}
-
-__device__ __forceinline__ void wave_reduce(double& m, double& s) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double om = __shfl_xor(m, o, 64);
-    const double os = __shfl_xor(s, o, 64);
-    m = om > m ? om : m;
-    s = s + os;
-  }
-}
 
 struct Lf2Params {
   const double* prev;  // u^{n−1}

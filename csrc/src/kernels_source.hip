@@ -23,16 +23,11 @@
 // scratch, 21296 B LDS each (two 11³ level buffers).
 #include <hip/hip_runtime.h>
 
+#include "wave3d/device_util.hpp"
 #include "wave3d/kernels.hpp"
 #include "wave3d/stencil.hpp"
 
 namespace wave3d {
-
-#define W3D_HIP_CHECK(expr)                                                                          \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess) ::wave3d::fail(std::string(#expr) + ": " + hipGetErrorString(_e));          \
-  } while (0)
 
 namespace {
 

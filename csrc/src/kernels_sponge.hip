@@ -20,20 +20,13 @@
 //     odd tile ends.
 #include <hip/hip_runtime.h>
 
+#include "wave3d/device_util.hpp"
 #include "wave3d/kernels.hpp"
 #include "wave3d/stencil.hpp"
 
 namespace wave3d {
 
-#define W3D_HIP_CHECK(expr)                                                                          \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess) ::wave3d::fail(std::string(#expr) + ": " + hipGetErrorString(_e));          \
-  } while (0)
-
 namespace {
-
-using v2d = double __attribute__((ext_vector_type(2)));
 
 constexpr int kTX = 8, kTY = 8, kTZ = 16;  // own nodes of a tile
 constexpr int kThreads = 512;

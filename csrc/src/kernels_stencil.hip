@@ -16,45 +16,14 @@
 //     halo rows then share one L2.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
+#include "wave3d/device_util.hpp"
 #include "wave3d/kernels.hpp"
+#include "wave3d/leapfrog_tiles.hpp"
 #include "wave3d/stencil.hpp"
 
 namespace wave3d {
 
-#define W3D_HIP_CHECK(expr)                                                                          \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess) ::wave3d::fail(std::string(#expr) + ": " + hipGetErrorString(_e));          \
-  } while (0)
-
 namespace {
-
-using v2d = double __attribute__((ext_vector_type(2)));
-
-constexpr int kLanes = 64;
-constexpr int kMaxBoxes = 6;
-
-__device__ __forceinline__ v2d ld2(const double* p) { return *reinterpret_cast<const v2d*>(p); }
-
-template <bool NT>
-__device__ __forceinline__ void st2(double* p, v2d v) {
-  if (NT)
-    __builtin_nontemporal_store(v, reinterpret_cast<v2d*>(p));
-  else
-    *reinterpret_cast<v2d*>(p) = v;
-}
-
-__device__ __forceinline__ void wave_reduce(double& m, double& s) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double om = __shfl_xor(m, o, 64);
-    const double os = __shfl_xor(s, o, 64);
-    m = om > m ? om : m;
-    s = s + os;
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // init + first step
@@ -113,14 +82,6 @@ __global__ __launch_bounds__(256) void k_init_first(const InitParams p) {
 // ---------------------------------------------------------------------------------------------------------------
 // leapfrog
 // ---------------------------------------------------------------------------------------------------------------
-struct TileBox {
-  i64 x0, x1;    // local x range
-  i64 y0, y1;    // local y range
-  i64 zo0, zo1;  // row-offset range of the updated nodes
-  i64 pz0, pz_end;
-  int ntz, nty, xchunk, tile_begin;
-};
-
 struct LfParams {
   const double* cur;
   double* out;
@@ -134,8 +95,7 @@ struct LfParams {
   SpongeView sp;
   // a speed field (the VARC instantiations): lam·c² per node in the solve layout, offset like cur / out
   const double* lamf;
-  int nbox, ntiles, nblocks, xcd_remap;
-  TileBox box[kMaxBoxes];
+  TileGrid g;
 };
 
 // DAMP: the damped update of the sponge layers (stencil.hpp leapfrog_damped). gx / rx of the plane are wave-uniform loads
@@ -146,26 +106,25 @@ template <int TY, bool CHECK, bool NT, bool DAMP = false, bool VARC = false>
 __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
   static_assert(TY >= 4, "halo slots need at least 128 + 2*TY threads");
   __shared__ v2d lds[2][TY + 2][kLanes + 2];
-  __shared__ double red_m[TY], red_s[TY];
 
   const int lane = static_cast<int>(threadIdx.x);
   const int row = static_cast<int>(threadIdx.y);
   const int tid = row * kLanes + lane;
 
   int tile = static_cast<int>(blockIdx.x);
-  if (p.xcd_remap) {
-    const int per = p.nblocks >> 3;
+  if (p.g.xcd_remap) {
+    const int per = p.g.nblocks >> 3;
     tile = (static_cast<int>(blockIdx.x) & 7) * per + (static_cast<int>(blockIdx.x) >> 3);
   }
-  if (tile >= p.ntiles) {
+  if (tile >= p.g.ntiles) {
     if (CHECK && tid == 0) p.partials[blockIdx.x] = make_double2(0.0, 0.0);
     return;
   }
   // select the box (scalar selects, no dynamic indexing of the kernarg struct)
-  TileBox B = p.box[0];
+  TileBox B = p.g.box[0];
 #pragma unroll
   for (int k = 1; k < kMaxBoxes; ++k)
-    if (k < p.nbox && tile >= p.box[k].tile_begin) B = p.box[k];
+    if (k < p.g.nbox && tile >= p.g.box[k].tile_begin) B = p.g.box[k];
 
   int t = tile - B.tile_begin;
   const int tz = t % B.ntz;
@@ -299,24 +258,8 @@ __global__ __launch_bounds__(kLanes* TY) void k_leapfrog_lds(const LfParams p) {
     rxp = nrxp;
   }
 
-  if (CHECK) {
-    wave_reduce(emax, esum);
-    if (lane == 0) {
-      red_m[row] = emax;
-      red_s[row] = esum;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double m = red_m[0], s = red_s[0];
-      for (int r = 1; r < TY; ++r) {
-        m = red_m[r] > m ? red_m[r] : m;
-        s += red_s[r];
-      }
-      p.partials[blockIdx.x] = make_double2(m, s);
-    }
-  }
+  if (CHECK) block_error_store<TY>(emax, esum, lane, row, tid, p.partials);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // leapfrog, variant 1: register-queue waves (no LDS, no barriers)
@@ -340,20 +283,20 @@ __global__ __launch_bounds__(64 * kWavesRq)
   const int lane = static_cast<int>(threadIdx.x) & 63;
   const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);  // wave-uniform: tile math stays scalar
   int blk = static_cast<int>(blockIdx.x);
-  if (p.xcd_remap) {
-    const int per = p.nblocks >> 3;
+  if (p.g.xcd_remap) {
+    const int per = p.g.nblocks >> 3;
     blk = (static_cast<int>(blockIdx.x) & 7) * per + (static_cast<int>(blockIdx.x) >> 3);
   }
   const int tile = blk * kWavesRq + wv;
   const int pidx = static_cast<int>(blockIdx.x) * kWavesRq + wv;
-  if (tile >= p.ntiles) {
+  if (tile >= p.g.ntiles) {
     if (CHECK && lane == 0) p.partials[pidx] = make_double2(0.0, 0.0);
     return;
   }
-  TileBox B = p.box[0];
+  TileBox B = p.g.box[0];
 #pragma unroll
   for (int k = 1; k < kMaxBoxes; ++k)
-    if (k < p.nbox && tile >= p.box[k].tile_begin) B = p.box[k];
+    if (k < p.g.nbox && tile >= p.g.box[k].tile_begin) B = p.g.box[k];
   int t = tile - B.tile_begin;
   const int tz = t % B.ntz;
   t /= B.ntz;
@@ -542,12 +485,15 @@ struct Plan {
 };
 
 Plan make_plan(const Layout& l, const LBox* boxes, int nbox, const LeapfrogTiling& t) {
-  W3D_REQUIRE(nbox >= 0 && nbox <= kMaxBoxes, "too many boxes in one leapfrog launch");
   const bool rq = t.variant == 1;
   W3D_REQUIRE(t.variant == 0 || t.variant == 1, "leapfrog variant must be 0 (lds) or 1 (rq)");
   W3D_REQUIRE(rq || t.ty == 4 || t.ty == 8 || t.ty == 16, "leapfrog tile rows must be 4, 8 or 16");
   W3D_REQUIRE(!rq || t.rows == 1 || t.rows == 2 || t.rows == 4 || t.rows == 8, "rows per wave must be 1, 2, 4 or 8");
-  const int trows = rq ? t.rows : t.ty;
+  for (int b = 0; b < nbox; ++b) {
+    const LBox& x = boxes[b];
+    W3D_REQUIRE(x.empty() || (x.x0 >= 0 && x.x1 <= l.nx && x.y0 >= 0 && x.y1 <= l.ny && x.z0 >= 0 && x.z1 <= l.nz),
+                "leapfrog box outside the owned region");
+  }
   Plan pl{};
   LfParams& p = pl.prm;
   p.plane = l.plane;
@@ -558,51 +504,11 @@ Plan make_plan(const Layout& l, const LBox* boxes, int nbox, const LeapfrogTilin
   p.zs = l.zs;
   // v0: one tile per workgroup, aim for 8 workgroups per CU; v1: one tile per wave, aim for 16 waves per CU
   const int target = t.target_blocks > 0 ? t.target_blocks : (rq ? 256 * 16 : 256 * 8);
-  // tiles before x-chunking, to spread the x-chunk count over boxes
-  i64 base_total = 0;
-  for (int b = 0; b < nbox; ++b) {
-    const LBox& x = boxes[b];
-    if (x.empty()) continue;
-    const i64 zo0 = x.z0 + 1 + l.zs, zo1 = x.z1 + 1 + l.zs;
-    base_total += ceil_div((zo1 + 1) / 2 - zo0 / 2, kLanes) * ceil_div(x.y1 - x.y0, trows);
-  }
-  const i64 want = base_total > 0 ? imax(1, ceil_div(target, base_total)) : 1;
-  int nb = 0, tiles = 0;
-  for (int b = 0; b < nbox; ++b) {
-    const LBox& x = boxes[b];
-    if (x.empty()) continue;
-    W3D_REQUIRE(x.x0 >= 0 && x.x1 <= l.nx && x.y0 >= 0 && x.y1 <= l.ny && x.z0 >= 0 && x.z1 <= l.nz,
-                "leapfrog box outside the owned region");
-    TileBox& tb = p.box[nb];
-    tb.x0 = x.x0;
-    tb.x1 = x.x1;
-    tb.y0 = x.y0;
-    tb.y1 = x.y1;
-    tb.zo0 = x.z0 + 1 + l.zs;
-    tb.zo1 = x.z1 + 1 + l.zs;
-    tb.pz0 = tb.zo0 / 2;
-    tb.pz_end = (tb.zo1 + 1) / 2;
-    W3D_REQUIRE(2 * tb.pz_end + 2 <= l.pitch, "row pitch too small for the pair tiling");
-    tb.ntz = static_cast<int>(ceil_div(tb.pz_end - tb.pz0, kLanes));
-    tb.nty = static_cast<int>(ceil_div(x.y1 - x.y0, trows));
-    const i64 nxb = x.x1 - x.x0;
-    const i64 min_chunk = 16;
-    i64 chunk = imax(min_chunk, ceil_div(nxb, want));
-    chunk = imin(chunk, nxb);
-    tb.xchunk = static_cast<int>(chunk);
-    const i64 nxc = ceil_div(nxb, chunk);
-    tb.tile_begin = tiles;
-    const i64 bt = static_cast<i64>(tb.ntz) * tb.nty * nxc;
-    W3D_REQUIRE(tiles + bt < (1ll << 30), "too many tiles");
-    tiles += static_cast<int>(bt);
-    ++nb;
-  }
-  p.nbox = nb;
-  p.ntiles = tiles;
-  p.xcd_remap = t.xcd_remap ? 1 : 0;
-  const int units = rq ? static_cast<int>(ceil_div(tiles, kWavesRq)) : tiles;  // workgroups
+  plan_tiles(l, boxes, nbox, rq ? t.rows : t.ty, 16, target, "", p.g);
+  p.g.xcd_remap = t.xcd_remap ? 1 : 0;
+  const int units = rq ? static_cast<int>(ceil_div(p.g.ntiles, kWavesRq)) : p.g.ntiles;  // workgroups
   pl.nblocks = t.xcd_remap ? static_cast<int>(round_up(units, 8)) : units;
-  p.nblocks = pl.nblocks;
+  p.g.nblocks = pl.nblocks;
   pl.npartials = rq ? pl.nblocks * kWavesRq : pl.nblocks;
   return pl;
 }
